@@ -1,8 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- SpectralConv forward+backward throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: set-up, the timed region of the contract with its clock settling (see below;
+`value` / `ms_per_step` are EXACTLY K timed steps), the outputs of the last step when --dump-outputs DIR is given
+(dump_outputs), then ONE JSON line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (the ms
+of one timed step), `config`, `clock_settle` and, with collectives, `collectives`.  Everything else described below -- `extra.*`, `roofline`, `step_roofline`, `stages`, the `cold_start`
+region, `gpu_reference_baseline`, `cpu_baseline`, `configs` -- is measured only with --full (the --no-* switches
+then leave parts of it out).
 
 A "step" = one forward + backward of ONE SpectralConv layer (grads for x, W, bias) over one
 batch of synthetic fields already resident in HBM.  Default workload = BASELINE configs[1]:
@@ -27,7 +34,8 @@ ranks) is run TWICE: straight after set-up (`cold_start` on the line) and again 
 back to back (`clock_settle`); `value` / `ms_per_step` are the second, settled region.  MI355X clocks need ~20 ms of
 sustained load to settle -- the first ~30 steps after any idle period run 10-25 % slower
 (profiles/r02_clock_ramp.txt) -- so a 25-step region straight after start-up measures the governor, not the kernels
-(see timed_steps and DESIGN.md 5).  --settle-ms 0 reports the cold region alone.
+(see timed_steps and DESIGN.md 5).  --settle-ms 0 reports the cold region alone.  A plain run (no --full) runs the same
+protocol but reports the settled region alone: its cold region only sizes the settling.
 """
 import argparse
 import json
@@ -91,6 +99,13 @@ def parse():
                     help="modeshard on ONE device, TIMING ONLY: the contraction of the mode-parallel layer runs on 1 / V of the "
                          "mode rows for V times the local batch -- the per-rank load of a V-rank group (transforms and the "
                          "degenerate exchanges are this rank's real ones; the numbers it computes are not the layer's)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: extra.*, roofline, stages, the cold region, "
+                         "gpu_reference_baseline, cpu_baseline, configs (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (y, x.grad, every parameter's .grad) "
+                         "as DIR/<name>.npy, float32, a seeded sample where an array exceeds its share of 64 MB "
+                         "(dump_outputs)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra.* measurements")
     ap.add_argument("--no-gpu-reference", action="store_true", help="skip gpu_reference_baseline")
     ap.add_argument("--force-generic", action="store_true", help="A/B: skip the fused FFT kernels")
@@ -588,6 +603,20 @@ def compact_configs(out, extra, world):
     return c
 
 
+def plan_names(spatial, n_modes, flags, io="f32"):
+    """The kernel names stage_profile returns, read from the forward plan alone (no launch)."""
+    from neuraloperator_amd import _lib
+    from neuraloperator_amd.engine import get_plan
+    from neuraloperator_amd.modes import halve_last_mode, kept_block
+
+    lib = _lib.get_lib()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    nm = halve_last_mode(n_modes)
+    kept, _ = kept_block(spatial, nm, nm)
+    plan = get_plan(dev, spatial, kept, "forward", flags | (_lib.SC_PLAN_IO_BF16 if io == "bf16" else 0))
+    return {"fwd": lib.plan_kernel_name(plan, 0), "inv": lib.plan_kernel_name(plan, 1), "fast": lib.plan_is_fast(plan)}
+
+
 def engine_path(names):
     """Which transform kernels the plan of this workload runs (sc_plan_kernel_name): the fused one-image-per-workgroup
     FFT (256-wide grids), the two-pass factorised FFT (512 / 1024 per axis), the factorised plane kernels (128 x 128 or 64 x 64
@@ -788,6 +817,32 @@ def timed_steps(step, steps, warmup, dist, dev, share, settle_ms=SETTLE_MS):
     return _timed_region(step, steps, warmup, dist, dev, share), cold, n
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: every array of one run together
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: every tensor of `outputs` ({name: tensor}) as <out_dir>/<name>.npy, float32 (complex tensors as their
+    real view, trailing axis of 2).  A tensor of more values than its equal share of `budget` bytes is written as a fixed
+    sample instead: 1-D, the values at the sorted flat indices drawn without replacement by numpy's generator seeded with 0
+    -- the same indices for the same shape in every run, so that two builds can be compared value for value.
+    Returns {name: [shape, values written]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (budget // max(len(outputs), 1) - 128) // 4      # 128: the .npy header
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        a = t
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+        written[name] = [list(t.shape), a.numel()]
+    return written
+
+
 def build_case(parallel, workload, world, dev, flags, io_dtype, dist, seed, conv_kwargs=None, mp_kwargs=None):
     """(step fn, per-GPU batch, global batch, scaling, parallelism tag, conv) of one measurement.
     conv_kwargs: extra constructor arguments of the single-GPU layer (extra.tfno_rank01: Tucker weights)."""
@@ -838,6 +893,7 @@ def build_case(parallel, workload, world, dev, flags, io_dtype, dist, seed, conv
         y.backward(g)
         if post is not None:
             post()
+        step.y = y.detach()                              # the last step's output (--dump-outputs), without its graph
 
     step.x, step.g = x, g                                # --graph captures the same step on the same tensors
     return step, b_local, global_batch, scaling, par, conv
@@ -1114,15 +1170,25 @@ def main():
     graphed = launch_tag.startswith("hipGraph")
     mappings.A2A_STATS.update(calls=0, bytes=0)
     ms, ms_cold, n_settle = timed_steps(step, args.steps, args.warmup, dist, dev, share, args.settle_ms)
+    n_timed = (args.steps + args.warmup) * (2 if n_settle else 1) + n_settle
     value = global_batch / (ms / 1e3)
     a2a = dict(mappings.A2A_STATS)
-    n_timed = (args.steps + args.warmup) * (2 if n_settle else 1) + n_settle
+    if args.dump_outputs:
+        # what a caller of the timed step holds after its last step: the output, the gradient of x, every parameter's
+        # gradient (a hipGraph replay leaves them in the captured tensors); one file set per rank on N GPUs
+        y_last = step.__self__.output if graphed else case[0].y
+        outs = {"y": y_last, "grad_x": case[0].x.grad}
+        outs.update(("grad_" + n.replace(".", "_"), p.grad) for n, p in conv.named_parameters() if p.grad is not None)
+        d = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+        wrote = dump_outputs(outs, d, DUMP_BYTES // world)
+        print("[bench] --dump-outputs:", d, json.dumps(wrote), file=sys.stderr, flush=True)
+        del y_last, outs
     del step, conv, case
     torch.cuda.empty_cache()
 
-    # ---- extra measurements (same launch, same W + K protocol): see the module docstring
+    # ---- extra measurements (--full; same launch, same W + K protocol): see the module docstring
     extra = {}
-    if not args.no_extras and args.workload == "fno2d_256_m64_c64_b32" and args.io == "f32":
+    if args.full and not args.no_extras and args.workload == "fno2d_256_m64_c64_b32" and args.io == "f32":
         # every BASELINE config on the driver-timed line: name, parallelism, workload,
         # storage type of the real tensors, extra constructor arguments.  Each runs the contract's own W + K steps (after the same settling as the headline).
         f32, bf16 = torch.float32, torch.bfloat16
@@ -1196,47 +1262,50 @@ def main():
     if rank == 0:
         nm = halve_last_mode(n_modes)
         kept, _ = kept_block(spatial, nm, nm)
-        R, Wb, S, total = alg_bytes(b_local, C, spatial, kept, 2 if args.io == "bf16" else 4)
-        stages, names = stage_profile(B if par.startswith(("modeshard", "pencil")) else b_local, C, spatial, n_modes,
-                                      flags, args.stage_iters, args.io)
-        dom = max(stages, key=lambda k: stages[k]["ms"])
-        kern = names["fwd"] if dom in ("fwd_transform", "adj_c2r_transform") else \
-            names["inv"] if dom in ("inv_transform", "adj_r2c_transform") else \
-            "k_modegemm_dma_bwd" if dom == "contract_bwd" else "k_modegemm_dma"
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.isfile(tpath):
-            try:
-                tkey = args.workload + ("_bf16io" if args.io == "bf16" else "")
-                traffic = json.load(open(tpath)).get(tkey, {}).get(dom) or None     # (0 = the regeneration did not see the kernel)
-            except Exception:
-                traffic = None
-        # the dominant kernel's own duration: back-to-back launches where that is measured (transforms), else in sequence
-        dom_ms = stages[dom].get("ms_back_to_back", stages[dom]["ms"])
-        dom_gbs = round(stages[dom]["alg_bytes"] / dom_ms / 1e6, 1)
-        traffic_source = ("profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel, gfx950 "
-                          "corrections applied; not re-measured by this run)")
-        step_tab = None
-        if world == 1 and not args.no_pmc and args.io == "f32" and not args.plan_flags and not args.force_generic:
-            torch.cuda.synchronize()
-            live, note, step_tab = measure_traffic_live(WORKLOADS[args.workload], kern)
-            if live is not None:
-                traffic_lookup, traffic, traffic_source = traffic, live, note
-                if traffic_lookup:
-                    traffic_source += f"; committed lookup (profiles/pmc_traffic.json): {traffic_lookup}"
-            else:
-                traffic_source += f"; live counters unavailable ({note})"
-        roof = {"bound": "hbm", "kernel": kern, "stage": dom,
-                "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(dom_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "traffic_source": traffic_source,
-                "alg_bytes_per_launch": stages[dom]["alg_bytes"], "ms_per_launch": dom_ms,
-                "ms_per_launch_how": "2 x stage-iters launches back to back between one pair of events"
-                                     if "ms_back_to_back" in stages[dom] else "in the layer's sequence, an event each side"}
-        step_gbs = total / ms / 1e6
-        copy_gbs = device_copy_ceiling(R)
-        roof["measured_copy_GBs"] = copy_gbs
-        roof["frac_of_measured_copy"] = round(dom_gbs / copy_gbs, 4)
+        if args.full:
+            R, Wb, S, total = alg_bytes(b_local, C, spatial, kept, 2 if args.io == "bf16" else 4)
+            stages, names = stage_profile(B if par.startswith(("modeshard", "pencil")) else b_local, C, spatial, n_modes,
+                                          flags, args.stage_iters, args.io)
+            dom = max(stages, key=lambda k: stages[k]["ms"])
+            kern = names["fwd"] if dom in ("fwd_transform", "adj_c2r_transform") else \
+                names["inv"] if dom in ("inv_transform", "adj_r2c_transform") else \
+                "k_modegemm_dma_bwd" if dom == "contract_bwd" else "k_modegemm_dma"
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.isfile(tpath):
+                try:
+                    tkey = args.workload + ("_bf16io" if args.io == "bf16" else "")
+                    traffic = json.load(open(tpath)).get(tkey, {}).get(dom) or None     # (0 = the regeneration did not see the kernel)
+                except Exception:
+                    traffic = None
+            # the dominant kernel's own duration: back-to-back launches where that is measured (transforms), else in sequence
+            dom_ms = stages[dom].get("ms_back_to_back", stages[dom]["ms"])
+            dom_gbs = round(stages[dom]["alg_bytes"] / dom_ms / 1e6, 1)
+            traffic_source = ("profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel, gfx950 "
+                              "corrections applied; not re-measured by this run)")
+            step_tab = None
+            if world == 1 and not args.no_pmc and args.io == "f32" and not args.plan_flags and not args.force_generic:
+                torch.cuda.synchronize()
+                live, note, step_tab = measure_traffic_live(WORKLOADS[args.workload], kern)
+                if live is not None:
+                    traffic_lookup, traffic, traffic_source = traffic, live, note
+                    if traffic_lookup:
+                        traffic_source += f"; committed lookup (profiles/pmc_traffic.json): {traffic_lookup}"
+                else:
+                    traffic_source += f"; live counters unavailable ({note})"
+            roof = {"bound": "hbm", "kernel": kern, "stage": dom,
+                    "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(dom_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "traffic_source": traffic_source,
+                    "alg_bytes_per_launch": stages[dom]["alg_bytes"], "ms_per_launch": dom_ms,
+                    "ms_per_launch_how": "2 x stage-iters launches back to back between one pair of events"
+                                         if "ms_back_to_back" in stages[dom] else "in the layer's sequence, an event each side"}
+            step_gbs = total / ms / 1e6
+            copy_gbs = device_copy_ceiling(R)
+            roof["measured_copy_GBs"] = copy_gbs
+            roof["frac_of_measured_copy"] = round(dom_gbs / copy_gbs, 4)
+        else:                                            # the config's engine_path without timing the stages
+            names = plan_names(spatial, n_modes, flags, args.io)
         out = {
             "metric": "FNO SpectralConv fwd+bwd samples/sec",
             "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -1250,27 +1319,30 @@ def main():
                           if args.emulate_world > 1 else {}),
                        "real_tensor_io": args.io,
                        "weights": "dense complex64, random init"},
-            "roofline": roof,
-            "step_roofline": {"alg_bytes_per_step": total, "achieved_GBs": round(step_gbs, 1),
-                              "frac_of_8TBs": round(step_gbs / HBM_PEAK_GBS, 4),
-                              # the same figure for the contract's FIRST timed region (before the clocks have settled)
-                              "frac_of_8TBs_cold_start": round(total / ms_cold / 1e6 / HBM_PEAK_GBS, 4),
-                              "frac_of_measured_copy": round(step_gbs / copy_gbs, 4),
-                              "formula": "4R+3Wb+9S (SURVEY.md 8d), per GPU" +
-                                         (", R at 2 bytes per value" if args.io == "bf16" else ""),
-                              **({"traffic": step_tab["step_traffic_B"],
-                                  "traffic_over_alg_bytes": round(step_tab["step_traffic_B"] / total, 3),
-                                  "traffic_kernels": {k: v["traffic_B"] for k, v in step_tab["kernels"].items()}}
-                                 if step_tab else {})},
-            "stages": stages,
-            "cold_start": {"ms_per_step": round(ms_cold, 4), "value": round(global_batch / (ms_cold / 1e3), 2),
-                           "what": f"the same {args.warmup} untimed + {args.steps} timed steps straight after set-up, "
-                                   "before the clocks have settled (first region; `value` is the second)"},
-            "clock_settle": {"steps": n_settle, "ms": args.settle_ms,
-                             "what": "untimed repetitions of the same step between the two timed regions "
-                                     "(profiles/r02_clock_ramp.txt: the first ~30 steps after any idle period run "
-                                     "10-25 % slower)"},
         }
+        if args.full:
+            out.update({
+                "roofline": roof,
+                "step_roofline": {"alg_bytes_per_step": total, "achieved_GBs": round(step_gbs, 1),
+                                  "frac_of_8TBs": round(step_gbs / HBM_PEAK_GBS, 4),
+                                  # the same figure for the contract's FIRST timed region (before the clocks have settled)
+                                  "frac_of_8TBs_cold_start": round(total / ms_cold / 1e6 / HBM_PEAK_GBS, 4),
+                                  "frac_of_measured_copy": round(step_gbs / copy_gbs, 4),
+                                  "formula": "4R+3Wb+9S (SURVEY.md 8d), per GPU" +
+                                             (", R at 2 bytes per value" if args.io == "bf16" else ""),
+                                  **({"traffic": step_tab["step_traffic_B"],
+                                      "traffic_over_alg_bytes": round(step_tab["step_traffic_B"] / total, 3),
+                                      "traffic_kernels": {k: v["traffic_B"] for k, v in step_tab["kernels"].items()}}
+                                     if step_tab else {})},
+                "stages": stages,
+                "cold_start": {"ms_per_step": round(ms_cold, 4), "value": round(global_batch / (ms_cold / 1e3), 2),
+                               "what": f"the same {args.warmup} untimed + {args.steps} timed steps straight after set-up, "
+                                       "before the clocks have settled (first region; `value` is the second)"},
+            })
+        out["clock_settle"] = {"steps": n_settle, "ms": args.settle_ms,
+                               "what": "untimed repetitions of the same step between the two timed regions "
+                                       "(profiles/r02_clock_ramp.txt: the first ~30 steps after any idle period run "
+                                       "10-25 % slower)"}
         if world > 1 or parallel == "modeshard":
             from neuraloperator_amd.mpu import peer_exchange, rccl_native
             native = rccl_native.active()
@@ -1290,11 +1362,12 @@ def main():
                                   else "during the timed steps"}
         if extra:
             out["extra"] = extra
-        if world == 1 and not args.no_gpu_reference and args.io == "f32":
+        if args.full and world == 1 and not args.no_gpu_reference and args.io == "f32":
             out["gpu_reference_baseline"] = gpu_reference_baseline(b_local, C, spatial, n_modes, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(args.workload)
-        out["configs"] = compact_configs(out, extra, world)   # LAST key: <= 1500 characters (tests/test_bench_contract.py)
+        if args.full:
+            out["configs"] = compact_configs(out, extra, world)   # LAST key: <= 1500 characters (tests/test_bench_contract.py)
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)
         print(json.dumps(out), flush=True)

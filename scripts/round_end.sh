@@ -6,8 +6,8 @@ O=gpurun_out/${1:-rz}; mkdir -p $O
 export TMPDIR=/tmp
 (timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -60) > $O/pytest.log
 (python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -12) > $O/smoke.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gpu-reference --no-extras --no-pmc > $GRAFT_REPO_ROOT/$O/bench_prof.json 2> $GRAFT_REPO_ROOT/$O/bench_prof.err)
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
+R=$PWD; (cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-gpu-reference --no-extras --no-pmc > $R/$O/bench_prof.json 2> $R/$O/bench_prof.err)
 python scripts/rocprof_summary.py /tmp/prof > $O/kernel_stats.txt 2>&1
 for wl in tucker:32,64,256,256,64,64 dense:8,32,128,128,128,32,32,32 dense:4,128,1024,1024,256,256; do
   k=${wl%%:*}; s=${wl#*:}; n=$(echo $s | tr ',' '_')

@@ -42,6 +42,22 @@ def test_settle_zero_reports_the_cold_region(bench):
     assert count[0] == 5 and n == 0 and ms == cold
 
 
+def test_dump_outputs_writes_float32_within_the_budget(bench, tmp_path):
+    import numpy as np
+    torch.manual_seed(0)
+    outs = {"y": torch.randn(64, 1000), "grad_w": torch.randn(8, 3, dtype=torch.cfloat), "grad_b": torch.randn(5).bfloat16()}
+    got = bench.dump_outputs(outs, str(tmp_path / "a"), budget=3 * (4 * 1000 + 128))
+    assert got == {"y": [[64, 1000], 1000], "grad_w": [[8, 3, 2], 48], "grad_b": [[5], 5]}
+    y = np.load(tmp_path / "a" / "y.npy")
+    w = np.load(tmp_path / "a" / "grad_w.npy")
+    assert y.dtype == w.dtype == np.float32 and y.shape == (1000,) and w.shape == (8, 3, 2)
+    assert np.array_equal(w, torch.view_as_real(outs["grad_w"]).numpy())
+    assert np.isin(y, outs["y"].numpy()).all()                           # a sample of the values, not a reduction
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 3 * (4 * 1000 + 128)
+    bench.dump_outputs(outs, str(tmp_path / "b"), budget=3 * (4 * 1000 + 128))
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), y)           # the same sample in every run
+
+
 def test_alg_bytes_metric_shape(bench):
     # 4 R + 3 Wb + 9 S = 2,666.5 MB per 32-sample step at the metric shape
     R, Wb, S, total = bench.alg_bytes(32, 64, (256, 256), [64, 33], 4)
