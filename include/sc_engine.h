@@ -228,6 +228,22 @@ int sc_modegemm_path(const sc_modegemm_desc* d);
  * float16 result of the inverse transform). */
 int sc_round_f16(const float* in, float* out, int64_t n, void* stream);
 
+/* ---- 2-D bicubic resample of a ROW RANGE of a global grid (the skip path of the spatially decomposed layer) ----
+ * resample(x, 1.0, [2, 3], output_shape) of neuralop/layers/resample.py:49-52, i.e. F.interpolate(mode="bicubic",
+ * align_corners=True) of a global (h_in, w_in) grid to (h_out, w_out), evaluated on one rank's rows.  x holds the
+ * global input rows [src_row0, src_row0 + rows_in) of `images` images, (images, rows_in, w_in) fp32 contiguous; y is
+ * the global output rows [out_row0, out_row0 + rows_out), (images, rows_out, w_out).  ATen's arithmetic: scale =
+ * (in - 1) / (out - 1) in fp32 (0 when out == 1), source index scale * dst, taps floor - 1 .. floor + 2 clamped to the
+ * GLOBAL grid, cubic convolution A = -0.75.  The input rows must cover every tap of the output rows (else an error);
+ * the column upsampling factor is at most ~45.
+ * Backward: gx (images, rows_in, w_in) OVERWRITTEN with the adjoint of the forward applied to gy (images, rows_out,
+ * w_out) -- the part of the input gradient these output rows contribute, halo rows included; deterministic gather
+ * (no atomics): two runs give the same bits. */
+int sc_bicubic_rows_forward(const float* x, float* y, int64_t images, int64_t rows_in, int64_t w_in, int64_t src_row0,
+                            int64_t h_in, int64_t h_out, int64_t w_out, int64_t out_row0, int64_t rows_out, void* stream);
+int sc_bicubic_rows_backward(const float* gy, float* gx, int64_t images, int64_t rows_in, int64_t w_in, int64_t src_row0,
+                             int64_t h_in, int64_t h_out, int64_t w_out, int64_t out_row0, int64_t rows_out, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

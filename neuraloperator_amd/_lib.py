@@ -170,7 +170,7 @@ class ScEngineLib:
                "sc_tucker_chain_backward_fused_workspace_bytes", "sc_peer_window_alloc", "sc_peer_window_open",
                "sc_peer_window_close", "sc_peer_window_free", "sc_peer_all_to_all", "sc_peer_window_control", "sc_pointwise_linear_forward_ex",
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
-               "sc_pointwise_block_backward_supported"]
+               "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -313,6 +313,9 @@ class ScEngineLib:
         L.sc_tucker_chain_backward_fused.restype = c_int
         L.sc_round_f16.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
         L.sc_round_f16.restype = c_int
+        for s in ("sc_bicubic_rows_forward", "sc_bicubic_rows_backward"):
+            getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 9 + [c_void_p]
+            getattr(L, s).restype = c_int
         L.sc_last_error.restype = c_char_p
         L.sc_version.restype = c_char_p
         L.sc_plan_kernel_name.argtypes = [c_void_p, c_int]
@@ -567,6 +570,19 @@ class ScEngineLib:
     def round_f16(self, in_ptr, out_ptr, n, stream=0):
         """out = float16(in) in fp32 storage (the cast points of fno_block_precision half / mixed)."""
         self._check(self.lib.sc_round_f16(in_ptr, out_ptr, n, stream))
+
+    def bicubic_rows_forward(self, x_ptr, y_ptr, images, rows_in, w_in, src_row0, h_in, h_out, w_out, out_row0,
+                             rows_out, stream=0):
+        """rows [out_row0, + rows_out) of the bicubic (align_corners) resample of a global (h_in, w_in) grid to
+        (h_out, w_out), from its rows [src_row0, + rows_in)"""
+        self._check(self.lib.sc_bicubic_rows_forward(x_ptr, y_ptr, images, rows_in, w_in, src_row0, h_in, h_out, w_out,
+                                                     out_row0, rows_out, stream))
+
+    def bicubic_rows_backward(self, gy_ptr, gx_ptr, images, rows_in, w_in, src_row0, h_in, h_out, w_out, out_row0,
+                              rows_out, stream=0):
+        """gx (images, rows_in, w_in) overwritten with the adjoint of bicubic_rows_forward applied to gy"""
+        self._check(self.lib.sc_bicubic_rows_backward(gy_ptr, gx_ptr, images, rows_in, w_in, src_row0, h_in, h_out,
+                                                      w_out, out_row0, rows_out, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

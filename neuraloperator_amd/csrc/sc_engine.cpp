@@ -42,6 +42,7 @@
 #include "sc_kernels_fmx.h"
 #include "sc_kernels_tkchain.h"
 #include "sc_kernels_peer.h"
+#include "sc_kernels_bicubic.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -3371,6 +3372,75 @@ extern "C" int sc_round_f16(const float* in, float* out, int64_t n, void* stream
   if (blocks > 16384) blocks = 16384;
   SC_LAUNCH(k_round_f16, dim3((unsigned)blocks), dim3(SC_BLOCK), 0, (sc_stream_t)stream, in, out, n, blocks * SC_BLOCK);
   return sc_check_launch("k_round_f16");
+}
+
+// ---- 2-D bicubic resample of a row range of a global grid (sc_kernels_bicubic.h) --------------------------------
+static float sc_bicubic_scale(int64_t in, int64_t out) {            // ATen's area_pixel_compute_scale, align_corners
+  return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f;
+}
+
+static int sc_bicubic_args(BicubicArgs& g, int64_t images, int64_t rows_in, int64_t w_in, int64_t src_row0, int64_t h_in,
+                           int64_t h_out, int64_t w_out, int64_t out_row0, int64_t rows_out) {
+  SC_CHECK_ARG(images >= 0 && rows_in > 0 && w_in > 0 && h_in > 0 && h_out > 0 && w_out > 0 && rows_out > 0,
+               "bicubic rows: empty grid");
+  SC_CHECK_ARG(h_in < (1 << 24) && w_in < (1 << 24) && h_out < (1 << 24) && w_out < (1 << 24),
+               "bicubic rows: grid sides must be below 2^24");
+  SC_CHECK_ARG(src_row0 >= 0 && src_row0 + rows_in <= h_in, "bicubic rows: input rows outside the global grid");
+  SC_CHECK_ARG(out_row0 >= 0 && out_row0 + rows_out <= h_out, "bicubic rows: output rows outside the global grid");
+  g.images = images;
+  g.rows_in = (int)rows_in;
+  g.w_in = (int)w_in;
+  g.src_row0 = (int)src_row0;
+  g.h_in = (int)h_in;
+  g.out_row0 = (int)out_row0;
+  g.rows_out = (int)rows_out;
+  g.h_out = (int)h_out;
+  g.w_out = (int)w_out;
+  g.sy = sc_bicubic_scale(h_in, h_out);
+  g.sx = sc_bicubic_scale(w_in, w_out);
+  // the rows the output rows' taps read must all be in the buffer (the same fp32 products as the kernels)
+  const int64_t f_lo = (int64_t)std::floor(g.sy * (float)out_row0);
+  const int64_t f_hi = (int64_t)std::floor(g.sy * (float)(out_row0 + rows_out - 1));
+  const int64_t need_lo = f_lo - 1 < 0 ? 0 : f_lo - 1;
+  const int64_t need_hi = f_hi + 2 > h_in - 1 ? h_in - 1 : f_hi + 2;
+  SC_CHECK_ARG(need_lo >= src_row0 && need_hi < src_row0 + rows_in,
+               "bicubic rows: the input rows do not cover the taps of the output rows");
+  // output columns one backward workgroup stages: floor(sx x) in [c0 - 2, c0 + 256]
+  const double span = g.sx > 0.0f ? (256.0 + 3.0) / (double)g.sx + 2.0 : 1.0;
+  SC_CHECK_ARG(span <= (double)BICUBIC_LDS_MAX, "bicubic rows: column upsampling factor above ~45 is not supported");
+  return 0;
+}
+
+extern "C" int sc_bicubic_rows_forward(const float* x, float* y, int64_t images, int64_t rows_in, int64_t w_in,
+                                       int64_t src_row0, int64_t h_in, int64_t h_out, int64_t w_out, int64_t out_row0,
+                                       int64_t rows_out, void* stream) {
+  BicubicArgs g;
+  if (sc_bicubic_args(g, images, rows_in, w_in, src_row0, h_in, h_out, w_out, out_row0, rows_out)) return 1;
+  if (images == 0) return 0;
+  SC_CHECK_ARG(x && y, "null argument");
+  const unsigned gx = (unsigned)((w_out + 255) / 256), gy = (unsigned)((rows_out + BICUBIC_TY - 1) / BICUBIC_TY);
+  for (int64_t i0 = 0; i0 < images; i0 += 32768) {
+    const int64_t n = images - i0 < 32768 ? images - i0 : 32768;
+    SC_LAUNCH(k_bicubic_rows_fwd, dim3(gx, gy, (unsigned)n), dim3(256), 0, (sc_stream_t)stream,
+              x + i0 * rows_in * w_in, y + i0 * rows_out * w_out, g);
+  }
+  return sc_check_launch("k_bicubic_rows_fwd");
+}
+
+extern "C" int sc_bicubic_rows_backward(const float* gy, float* gx, int64_t images, int64_t rows_in, int64_t w_in,
+                                        int64_t src_row0, int64_t h_in, int64_t h_out, int64_t w_out, int64_t out_row0,
+                                        int64_t rows_out, void* stream) {
+  BicubicArgs g;
+  if (sc_bicubic_args(g, images, rows_in, w_in, src_row0, h_in, h_out, w_out, out_row0, rows_out)) return 1;
+  if (images == 0) return 0;
+  SC_CHECK_ARG(gy && gx, "null argument");
+  const unsigned bx = (unsigned)((w_in + 255) / 256), by = (unsigned)((rows_in + BICUBIC_TR - 1) / BICUBIC_TR);
+  for (int64_t i0 = 0; i0 < images; i0 += 32768) {
+    const int64_t n = images - i0 < 32768 ? images - i0 : 32768;
+    SC_LAUNCH(k_bicubic_rows_bwd, dim3(bx, by, (unsigned)n), dim3(256), 0, (sc_stream_t)stream,
+              gy + i0 * rows_out * w_out, gx + i0 * rows_in * w_in, g);
+  }
+  return sc_check_launch("k_bicubic_rows_bwd");
 }
 
 extern "C" int sc_modegemm_path(const sc_modegemm_desc* d) {

@@ -727,6 +727,38 @@ def round_f16(t):
     return RoundF16Fn.apply(t)
 
 
+class BicubicRowsFn(torch.autograd.Function):
+    """Rows [out_row0, out_row0 + out_rows) of F.interpolate(mode="bicubic", align_corners=True) of a global
+    (H_in, W_in) grid to (H_out, W_out) (resample.py:49-52), from x (B, C, R, W_in) = its global rows
+    [src_row0, src_row0 + R): sc_bicubic_rows_forward / _backward.  The gradient covers all R rows (halo rows
+    included: the caller's exchange returns them to their owners)."""
+
+    @staticmethod
+    def forward(ctx, x, in_grid, out_grid, src_row0, out_row0, out_rows):
+        _require_gpu(x, "x")
+        if x.dtype != torch.float32 or x.dim() != 4:
+            raise TypeError(f"bicubic rows: a (B, C, rows, W) float32 tensor, got {tuple(x.shape)} {x.dtype}")
+        x = x.contiguous()
+        b, c, r, w_in = (int(v) for v in x.shape)
+        geo = (r, w_in, int(src_row0), int(in_grid[0]), int(out_grid[0]), int(out_grid[1]), int(out_row0), int(out_rows))
+        if w_in != int(in_grid[1]):
+            raise ValueError(f"bicubic rows: input width {w_in} is not the grid's {in_grid[1]}")
+        y = torch.empty(b, c, int(out_rows), int(out_grid[1]), dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.get_lib().bicubic_rows_forward(x.data_ptr(), y.data_ptr(), b * c, *geo, _stream())
+        ctx.geo, ctx.shape = geo, (b, c)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.contiguous()
+        b, c = ctx.shape
+        gx = torch.empty(b, c, ctx.geo[0], ctx.geo[1], dtype=gy.dtype, device=gy.device)
+        with torch.cuda.device(gy.device):
+            _lib.get_lib().bicubic_rows_backward(gy.data_ptr(), gx.data_ptr(), b * c, *ctx.geo, _stream())
+        return gx, None, None, None, None, None
+
+
 class EngineOps:
     """The three local stages of a (mode-parallel) spectral layer on the MI355X engine."""
 
@@ -760,6 +792,12 @@ class EngineOps:
     def inverse_axis(self, xhat, n, rows):
         return TransformInverseFn.apply(xhat, None, [int(n)], self.fft_norm, self.flags | SC_PLAN_COMPLEX,
                                         [list(rows)], 0)
+
+    # the 2-d skip-path resample on a row range of a global grid (mpu.SpatialParallelSpectralConv.transform): x
+    # (B, C, R, W_in) holds global input rows [src_row0, src_row0 + R); returns output rows [out_row0, + out_rows)
+    @staticmethod
+    def interpolate_rows(x, in_grid, out_grid, src_row0, out_row0, out_rows):
+        return BicubicRowsFn.apply(x, list(in_grid), list(out_grid), int(src_row0), int(out_row0), int(out_rows))
 
 
 class EngineRawOps:

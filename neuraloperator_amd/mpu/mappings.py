@@ -71,6 +71,66 @@ def all_to_all(x, split_dim, cat_dim, group=None):
     return _AllToAll.apply(x, split_dim, cat_dim, group)
 
 
+# ---- halo exchange of a row-sharded tensor (the skip-path resample of mpu.SpatialParallelSpectralConv) ------------
+def _row_splits(h, ranges, p):
+    """[(a, b)] per peer q: the rows of rank p's shard [p h, (p + 1) h) inside peer q's range, local indices"""
+    out = []
+    for lo, hi in ranges:
+        a, b = max(lo, p * h), min(hi, (p + 1) * h)
+        out.append((a - p * h, b - p * h) if b > a else (0, 0))
+    return out
+
+
+def _rows_a2a(pieces, recv_rows, group):
+    """send pieces[q] (dim 0 = rows) to rank q; returns what every rank sent here, in rank order, as a list"""
+    send = torch.cat(pieces, 0)
+    recv = send.new_empty((sum(recv_rows), *send.shape[1:]))
+    dist.all_to_all_single(recv, send, output_split_sizes=list(recv_rows),
+                           input_split_sizes=[int(t.shape[0]) for t in pieces], group=group)
+    A2A_STATS["calls"] += 1
+    A2A_STATS["bytes"] += send.numel() * send.element_size()
+    return list(recv.split(list(recv_rows), 0))
+
+
+class _ExchangeRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dim, ranges, group):
+        p, n = dist.get_rank(group=group), _size(group)
+        h = x.shape[dim]
+        ctx.dim, ctx.group, ctx.h = dim, group, h
+        mine = _row_splits(h, ranges, p)                                # my rows each peer needs
+        theirs = [_row_splits(h, [ranges[p]], q)[0] for q in range(n)]  # each peer's rows I need
+        ctx.mine, ctx.theirs = mine, theirs
+        xt = x.movedim(dim, 0)
+        recv = _rows_a2a([xt[a:b].contiguous() for a, b in mine], [b - a for a, b in theirs], group)
+        return torch.cat(recv, 0).movedim(0, dim).contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        # the reverse exchange: every halo row's gradient goes back to its owner and is added there (rank order)
+        gt = g.movedim(ctx.dim, 0)
+        cuts = [b - a for a, b in ctx.theirs]
+        pieces = [t.contiguous() for t in gt.split(cuts, 0)]
+        recv = _rows_a2a(pieces, [b - a for a, b in ctx.mine], ctx.group)
+        gx = g.new_zeros((ctx.h, *gt.shape[1:]))
+        for (a, b), t in zip(ctx.mine, recv):
+            if b > a:
+                gx[a:b] += t
+        return gx.movedim(0, ctx.dim).contiguous(), None, None, None
+
+
+def exchange_rows(x, dim, ranges, group=None):
+    """``x`` is this rank's shard of a tensor row-sharded along ``dim`` (rank p owns rows [p h, (p + 1) h), h =
+    x.shape[dim]); ``ranges[q] = (lo, hi)`` is the global row range rank q needs (the same list on every rank).
+    Returns the rows [lo, hi) of this rank's range, gathered from their owners -- only those rows move, a range may
+    span several owners.  Autograd: the reverse exchange, halo-row gradients summed at their owners."""
+    group = group if group is not None else get_model_parallel_group()
+    if _size(group) == 1:
+        lo, hi = ranges[0]
+        return x if (lo, hi) == (0, x.shape[dim]) else x.narrow(dim, lo, hi - lo)
+    return _ExchangeRows.apply(x, dim, [tuple(int(v) for v in r) for r in ranges], group)
+
+
 # ---- the reference's four region mappings ----------------------------------------------------
 def _reduce(t, group):
     if _size(group) == 1:

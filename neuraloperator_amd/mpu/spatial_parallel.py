@@ -28,6 +28,16 @@ last-dim rule, modes.analysis_freqs), ``separable=True`` (one (C, modes) weight,
 resolution along EVERY dim (the synthesis maps of
 modes.synthesis_freqs on the local transform and on the axis pass).
 
+The skip path's resample, ``transform(x, output_shape)`` (resample.py:7-71, what FNOBlocks calls on both skips of
+every block, fno_block.py:377-392), works on the row shards too, so the layer runs inside FNOBlocks / FNO with a
+``resolution_scaling_factor`` or ``FNO.forward(x, output_shape=...)``.  2-d: bicubic interpolation (:49-52) -- each
+rank's output rows read a contiguous range of global input rows (its own plus at most a few of its neighbours', found
+with the kernel's own fp32 index arithmetic, ``bicubic_source_rows``); ``mappings.exchange_rows`` moves exactly those
+rows (gradients of halo rows go back to their owners) and the engine's ``interpolate_rows`` stage
+(include/sc_engine.h, sc_bicubic_rows_forward) interpolates them.  3-d and up: the spectral resample (:54-66) as the
+forward pipeline above without the contraction (modes.resample_block's maps).  ``complex_data=True`` is not available
+on the skip path.
+
 Every local stage is an engine transform over fewer dims (a (N-1)-d real plan with the local rows folded into the
 channel count, and a 1-d complex plan with an explicit centred frequency map -- include/sc_engine.h,
 sc_plan_desc.freq); the separable N-d transform of spectral_convolution.py:443-449 / :531-559 is the product of
@@ -35,13 +45,27 @@ the two.  One all-to-all each way moves the truncated spectrum only (k2/d2 of th
 same pipeline mirrored.  Each rank sees the whole batch for its mode columns: gW needs no all-reduce; the bias
 gradient is summed over the group (every rank saw different rows).
 """
+import numpy as np
 import torch
 from torch import nn
 
-from ..modes import analysis_freqs, halve_last_mode, kept_block, kept_block_complex, synthesis_freqs
+from ..modes import analysis_freqs, halve_last_mode, kept_block, kept_block_complex, resample_block, synthesis_freqs
 from ..spectral_conv import BaseSpectralConv
 from . import comm
-from .mappings import all_to_all
+from .mappings import all_to_all, exchange_rows
+
+
+def bicubic_source_rows(h_in, h_out, P):
+    """[(lo, hi)] per rank: the global input rows the taps of rank p's output rows [p h_out / P, (p + 1) h_out / P) of
+    a bicubic align_corners resample read -- ATen's fp32 index arithmetic, exactly as the kernel evaluates it
+    (include/sc_engine.h, sc_bicubic_rows_forward): floor(scale dst) - 1 .. + 2, clamped to the global grid."""
+    scale = np.float32(h_in - 1) / np.float32(h_out - 1) if h_out > 1 else np.float32(0)
+    rows = h_out // P
+
+    def fl(y):
+        return int(np.floor(np.float32(scale) * np.float32(y)))
+
+    return [(max(fl(p * rows) - 1, 0), min(fl((p + 1) * rows - 1) + 2, h_in - 1) + 1) for p in range(P)]
 
 
 def centred_rows(k, n):
@@ -159,9 +183,53 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
         self._n_modes = nm
 
     def transform(self, x, output_shape=None):
-        if output_shape is not None or self.resolution_scaling_factor is not None:
-            raise NotImplementedError("the skip path's resample needs whole rows: not on the spatially decomposed layer")
-        return x
+        """The skip path's resample (resample(x, 1.0, spatial dims, output_shape), resample.py:7-71) on this rank's rows:
+        ``output_shape`` is the FULL output grid, as in ``forward``; this rank returns its rows of the resampled grid.
+        2-d: bicubic interpolation (:49-52) on the rows of the shard plus the halo rows its output rows read
+        (mappings.exchange_rows, then the engine's interpolate_rows); 3-d and up: the spectral resample (:54-66) as
+        this layer's forward pipeline without the contraction."""
+        in_grid = [x.shape[2] * self.P] + list(x.shape[3:])
+        out_grid = self._out_grid(in_grid, output_shape)
+        if out_grid == in_grid:
+            return x
+        if self.complex_data:
+            raise NotImplementedError("complex_data=True: the skip path's resample of complex data is not available "
+                                      "on the spatially decomposed layer")
+        if self.order == 2:
+            return self._resample_bicubic(x, in_grid, out_grid)
+        return self._resample_spectral(x, in_grid, out_grid)
+
+    def _resample_bicubic(self, x, in_grid, out_grid):
+        ranges = bicubic_source_rows(in_grid[0], out_grid[0], self.P)
+        xh = exchange_rows(x, 2, ranges, group=self.group)                     # (B, C, rows of my range, W)
+        h_out = out_grid[0] // self.P
+        return self.ops.interpolate_rows(xh, in_grid, out_grid, ranges[self.rank][0], self.rank * h_out, h_out)
+
+    def _resample_spectral(self, x, in_grid, out_grid):
+        b, c, h_loc = x.shape[:3]
+        kept, fa, fs = resample_block(in_grid, out_grid)
+        d1, d1_o, h_out, rest_o = in_grid[0], out_grid[0], out_grid[0] // self.P, out_grid[1:]
+        # 1. pruned transform over d2..dN on the local rows
+        xh = self.ops.forward_transform(x.float().reshape(b, c * h_loc, *in_grid[1:]), kept[1:], fa[1:])
+        xh = xh.reshape(b, c, h_loc, *kept[1:])
+        # 2. + 3. pad the second kept dim to a multiple of P, all-to-all: every row of this rank's columns
+        k2 = kept[1]
+        k2p = -(-k2 // self.P) * self.P
+        xh = _place_dim(xh, 3, 0, k2p)
+        xh = all_to_all(xh, split_dim=3, cat_dim=2, group=self.group)          # (B, C, d1, k2p/P, ..)
+        # 4. + 5. the sharded dim: kept signed rows of the old grid onto the same signed rows of the new one
+        xt = xh.movedim(2, -1).contiguous()
+        lead = xt.shape[:-1]
+        xa = self.ops.forward_axis(xt.reshape(b, -1, d1), kept[0], fa[0])
+        ya = self.ops.inverse_axis(xa, d1_o, fs[0])
+        ya = ya.reshape(*lead, d1_o).movedim(-1, 2).contiguous()               # (B, C, d1', k2p/P, ..)
+        # 6. all-to-all back, drop the padding
+        ya = all_to_all(ya, split_dim=2, cat_dim=3, group=self.group)          # (B, C, d1'/P, k2p, ..)
+        if k2p != k2:
+            ya = ya.narrow(3, 0, k2)
+        # 7. zero-padded inverse transform over d2..dN to the new grid
+        ya = ya.reshape(b, c * h_out, *kept[1:]).contiguous()
+        return self.ops.inverse_transform(ya, None, rest_o, list(fs[1:])).reshape(b, c, h_out, *rest_o)
 
     def _out_grid(self, in_grid, output_shape):
         """the full output grid (spectral_convolution.py:520-529: output_shape, else the scaled input grid)"""
