@@ -228,6 +228,24 @@ int sc_modegemm_path(const sc_modegemm_desc* d);
  * float16 result of the inverse transform). */
 int sc_round_f16(const float* in, float* out, int64_t n, void* stream);
 
+/* ---- the complex32 wire of the mode-parallel layer's half-precision exchanges (fno_block_precision "half" /
+ * "mixed") ----
+ * spec: complex64 (interleaved fp32) [n][c][k1][rest]; wire: complex32 (two float16 words, real part in the low half)
+ * in the rank-major send layout [P][n][c][rows][rest].  Global wire row w0 + r (rank (w0 + r) / rows, local row
+ * (w0 + r) % rows) holds spectrum row r; w0 + k1 <= P * rows.  Values are rounded with sc_round_f16 (nearest even,
+ * torch's cast).  P = 1, w0 = 0, k1 = rows: a plain complex64 <-> complex32 conversion.
+ *
+ * sc_wire_pack_c32: spec -> wire, every wire row outside [w0, w0 + k1) written zero.  Replaces the zero-filled
+ * (n, c, P rows, rest) staging tensor, the slice copy of the kept rows into it and the chunk-major send-buffer copy of
+ * the fp32 exchange (mpu.mappings.all_to_all) on the half-precision route of ModeParallelSpectralConv. */
+int sc_wire_pack_c32(const float* spec, void* wire, int64_t n, int64_t c, int64_t k1, int64_t rest, int64_t P,
+                     int64_t rows, int64_t w0, void* stream);
+
+/* sc_wire_unpack_c32: wire -> spec, rows [w0, w0 + k1) of the P * rows concatenation.  Replaces the rank-order
+ * concatenation copy after the fp32 exchange and the slice copy of the kept rows out of it. */
+int sc_wire_unpack_c32(const void* wire, float* spec, int64_t n, int64_t c, int64_t k1, int64_t rest, int64_t P,
+                       int64_t rows, int64_t w0, void* stream);
+
 /* ---- 2-D bicubic resample of a ROW RANGE of a global grid (the skip path of the spatially decomposed layer) ----
  * resample(x, 1.0, [2, 3], output_shape) of neuralop/layers/resample.py:49-52, i.e. F.interpolate(mode="bicubic",
  * align_corners=True) of a global (h_in, w_in) grid to (h_out, w_out), evaluated on one rank's rows.  x holds the

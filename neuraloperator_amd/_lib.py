@@ -170,7 +170,8 @@ class ScEngineLib:
                "sc_tucker_chain_backward_fused_workspace_bytes", "sc_peer_window_alloc", "sc_peer_window_open",
                "sc_peer_window_close", "sc_peer_window_free", "sc_peer_all_to_all", "sc_peer_window_control", "sc_pointwise_linear_forward_ex",
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
-               "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward"]
+               "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
+               "sc_wire_pack_c32", "sc_wire_unpack_c32"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -315,6 +316,9 @@ class ScEngineLib:
         L.sc_round_f16.restype = c_int
         for s in ("sc_bicubic_rows_forward", "sc_bicubic_rows_backward"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 9 + [c_void_p]
+            getattr(L, s).restype = c_int
+        for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
+            getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
         L.sc_last_error.restype = c_char_p
         L.sc_version.restype = c_char_p
@@ -570,6 +574,16 @@ class ScEngineLib:
     def round_f16(self, in_ptr, out_ptr, n, stream=0):
         """out = float16(in) in fp32 storage (the cast points of fno_block_precision half / mixed)."""
         self._check(self.lib.sc_round_f16(in_ptr, out_ptr, n, stream))
+
+    def wire_pack_c32(self, spec_ptr, wire_ptr, n, c, k1, rest, P, rows, w0, stream=0):
+        """complex64 [n, c, k1, rest] -> complex32 wire [P, n, c, rows, rest]: spectrum row r on global wire row w0 + r,
+        every other wire row zero"""
+        self._check(self.lib.sc_wire_pack_c32(spec_ptr, wire_ptr, n, c, k1, rest, P, rows, w0, stream))
+
+    def wire_unpack_c32(self, wire_ptr, spec_ptr, n, c, k1, rest, P, rows, w0, stream=0):
+        """complex32 wire [P, n, c, rows, rest] -> complex64 [n, c, k1, rest]: rows [w0, w0 + k1) of the P * rows
+        concatenation"""
+        self._check(self.lib.sc_wire_unpack_c32(wire_ptr, spec_ptr, n, c, k1, rest, P, rows, w0, stream))
 
     def bicubic_rows_forward(self, x_ptr, y_ptr, images, rows_in, w_in, src_row0, h_in, h_out, w_out, out_row0,
                              rows_out, stream=0):

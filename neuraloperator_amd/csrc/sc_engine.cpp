@@ -43,6 +43,7 @@
 #include "sc_kernels_tkchain.h"
 #include "sc_kernels_peer.h"
 #include "sc_kernels_bicubic.h"
+#include "sc_kernels_wire.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -3372,6 +3373,50 @@ extern "C" int sc_round_f16(const float* in, float* out, int64_t n, void* stream
   if (blocks > 16384) blocks = 16384;
   SC_LAUNCH(k_round_f16, dim3((unsigned)blocks), dim3(SC_BLOCK), 0, (sc_stream_t)stream, in, out, n, blocks * SC_BLOCK);
   return sc_check_launch("k_round_f16");
+}
+
+// ---- the complex32 wire of the half-precision exchanges (sc_kernels_wire.h) ------------------------------------------
+static int sc_wire_launch(const bool pack, const void* src, void* dst, int64_t n, int64_t c, int64_t k1, int64_t rest,
+                          int64_t P, int64_t rows, int64_t w0, void* stream) {
+  if (n == 0 || c == 0 || k1 == 0 || rest == 0) return 0;
+  SC_CHECK_ARG(src && dst, "null argument");
+  SC_CHECK_ARG(n > 0 && c > 0 && k1 > 0 && rest > 0 && P > 0 && rows > 0 && w0 >= 0, "wire: bad extents");
+  SC_CHECK_ARG(w0 + k1 <= P * rows, "wire: rows [w0, w0 + k1) past the P * rows wire rows");
+  SC_CHECK_ARG(rows <= INT32_MAX && k1 <= INT32_MAX, "wire: row count out of range");
+  // two elements per lane: even rows (a unit never straddles two) and 16 / 8-byte aligned complex64 / wire pointers
+  const bool v2 = rest % 2 == 0 && (uintptr_t)src % (pack ? 16 : 8) == 0 && (uintptr_t)dst % (pack ? 8 : 16) == 0;
+  const int64_t elems = pack ? P * n * c * rows * rest : n * c * k1 * rest;
+  WireArgs g;
+  g.src = src;
+  g.dst = dst;
+  g.units = v2 ? elems / 2 : elems;
+  g.rest = rest;
+  g.nc = n * c;
+  g.rows = (int)rows;
+  g.k1 = (int)k1;
+  g.w0 = (int)w0;
+  int64_t blocks = (g.units + 256 * WIRE_UNROLL - 1) / (256 * WIRE_UNROLL);
+  if (blocks > 2048) blocks = 2048;
+  g.stride = blocks * 256 * WIRE_UNROLL;
+  const sc_stream_t st = (sc_stream_t)stream;
+  if (pack) {
+    if (v2) SC_LAUNCH(k_wire_pack_c32<2>, dim3((unsigned)blocks), dim3(256), 0, st, g);
+    else SC_LAUNCH(k_wire_pack_c32<1>, dim3((unsigned)blocks), dim3(256), 0, st, g);
+    return sc_check_launch("k_wire_pack_c32");
+  }
+  if (v2) SC_LAUNCH(k_wire_unpack_c32<2>, dim3((unsigned)blocks), dim3(256), 0, st, g);
+  else SC_LAUNCH(k_wire_unpack_c32<1>, dim3((unsigned)blocks), dim3(256), 0, st, g);
+  return sc_check_launch("k_wire_unpack_c32");
+}
+
+extern "C" int sc_wire_pack_c32(const float* spec, void* wire, int64_t n, int64_t c, int64_t k1, int64_t rest, int64_t P,
+                                int64_t rows, int64_t w0, void* stream) {
+  return sc_wire_launch(true, spec, wire, n, c, k1, rest, P, rows, w0, stream);
+}
+
+extern "C" int sc_wire_unpack_c32(const void* wire, float* spec, int64_t n, int64_t c, int64_t k1, int64_t rest, int64_t P,
+                                  int64_t rows, int64_t w0, void* stream) {
+  return sc_wire_launch(false, wire, spec, n, c, k1, rest, P, rows, w0, stream);
 }
 
 // ---- 2-D bicubic resample of a row range of a global grid (sc_kernels_bicubic.h) --------------------------------

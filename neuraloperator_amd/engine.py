@@ -5,6 +5,7 @@ of the hot path runs in libsc_engine.so (hand-written HIP, include/sc_engine.h).
 """
 import atexit
 import collections
+import math
 import threading
 
 import torch
@@ -725,6 +726,40 @@ class RoundF16Fn(torch.autograd.Function):
 
 def round_f16(t):
     return RoundF16Fn.apply(t)
+
+
+def wire_pack_c32(spec, P, rows, w0):
+    """complex64 spectrum (n, C, k1, *rest) -> the complex32 wire (P, n, C, rows, *rest) of the half-precision exchange,
+    one 32-bit word per element (int32 storage: torch.complex32's bytes, real part in the low half).  Spectrum row r
+    lands on global wire row w0 + r of the P * rows concatenation, every other row is zero; values rounded with
+    sc_round_f16.  P = 1, w0 = 0, k1 = rows: a plain conversion.  No autograd (mpu.mappings.all_to_all_c32)."""
+    _require_gpu(spec, "spec")
+    if spec.dtype != torch.complex64 or spec.dim() < 3:
+        raise TypeError(f"wire_pack_c32: a (n, C, k1, ...) complex64 tensor, got {tuple(spec.shape)} {spec.dtype}")
+    spec = spec.contiguous()
+    n, c, k1 = (int(v) for v in spec.shape[:3])
+    rest = list(spec.shape[3:])
+    wire = torch.empty((int(P), n, c, int(rows), *rest), dtype=torch.int32, device=spec.device)
+    with torch.cuda.device(spec.device):
+        _lib.get_lib().wire_pack_c32(spec.data_ptr(), wire.data_ptr(), n, c, k1, math.prod(rest), int(P), int(rows),
+                                     int(w0), _stream())
+    return wire
+
+
+def wire_unpack_c32(wire, k1, w0):
+    """the complex32 wire (P, n, C, rows, *rest) (int32 words) -> complex64 (n, C, k1, *rest): rows [w0, w0 + k1) of the
+    P * rows concatenation.  P = 1, w0 = 0, k1 = rows: a plain conversion.  No autograd."""
+    _require_gpu(wire, "wire")
+    if wire.dtype != torch.int32 or wire.dim() < 4:
+        raise TypeError(f"wire_unpack_c32: a (P, n, C, rows, ...) int32 tensor, got {tuple(wire.shape)} {wire.dtype}")
+    wire = wire.contiguous()
+    P, n, c, rows = (int(v) for v in wire.shape[:4])
+    rest = list(wire.shape[4:])
+    spec = torch.empty((n, c, int(k1), *rest), dtype=torch.complex64, device=wire.device)
+    with torch.cuda.device(wire.device):
+        _lib.get_lib().wire_unpack_c32(wire.data_ptr(), spec.data_ptr(), n, c, int(k1), math.prod(rest), P, rows,
+                                       int(w0), _stream())
+    return spec
 
 
 class BicubicRowsFn(torch.autograd.Function):

@@ -71,6 +71,59 @@ def all_to_all(x, split_dim, cat_dim, group=None):
     return _AllToAll.apply(x, split_dim, cat_dim, group)
 
 
+# ---- the complex32 exchange of the half-precision mode-parallel route --------------------------------------------------
+def _c32_exchange(x, k1, w0, rows, to_rows, group):
+    """to_rows: x (n, C, k1, *rest) complex64 -> (P n, C, rows, *rest), this rank's wire rows of every rank's batch
+    (spectrum row r sits on global wire row w0 + r); else x (P n, C, rows, *rest) -> (n, C, k1, *rest), rows
+    [w0, w0 + k1) of this rank's batch gathered from every rank.  One all-to-all of the complex32 wire (engine
+    wire_pack_c32 / wire_unpack_c32), sent as int32 words: gloo and RCCL both move that type."""
+    from .. import engine
+    P = _size(group)
+    if to_rows:
+        wire = engine.wire_pack_c32(x, P, rows, w0)                            # (P, n, C, rows, rest)
+    else:
+        wire = engine.wire_pack_c32(x, 1, rows, 0)                             # (1, P n, C, rows, rest) = (P, n, ..)
+        wire = wire.view(P, x.shape[0] // P, *wire.shape[2:])
+    if dist.is_initialized():
+        recv = torch.empty_like(wire)
+        dist.all_to_all_single(recv, wire, group=group)
+        A2A_STATS["calls"] += 1
+        A2A_STATS["bytes"] += wire.numel() * wire.element_size()
+    else:
+        recv = wire                                                            # no process group: one rank, no wire
+    if to_rows:
+        return engine.wire_unpack_c32(recv.view(1, -1, *recv.shape[2:]), rows, 0)
+    return engine.wire_unpack_c32(recv, k1, w0)
+
+
+class _AllToAllC32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k1, w0, rows, to_rows, group):
+        ctx.cfg = (k1, w0, rows, to_rows, group)
+        return _c32_exchange(x, k1, w0, rows, to_rows, group)
+
+    @staticmethod
+    def backward(ctx, g):
+        # the adjoint of a row placement + exchange is the reverse exchange + the row window, on the same wire
+        k1, w0, rows, to_rows, group = ctx.cfg
+        return _c32_exchange(g.contiguous(), k1, w0, rows, not to_rows, group), None, None, None, None, None
+
+
+def all_to_all_c32(x, k1, w0, rows, to_rows, group=None):
+    """The mode exchange of the mode-parallel layer on a COMPLEX32 wire (4 bytes per mode instead of 8), forward and
+    backward.  to_rows=True: x (n, C, k1, *rest) is this rank's batch of the kept spectrum rows; kept row r travels to
+    the rank that owns global mode row w0 + r (rank (w0 + r) // rows of P blocks of ``rows``), the result (P n, C,
+    rows, *rest) is this rank's block of rows for every rank's batch (zero rows where no kept row lands).
+    to_rows=False: the inverse direction, (P n, C, rows, *rest) -> (n, C, k1, *rest).  Autograd: the same op in the
+    reverse direction, also on the complex32 wire.  The result is complex64 holding float16 values.
+
+    PRECONDITION: every value is rounded to float16 on the wire (sc_round_f16), so use it only where the consumer rounds
+    its input to float16 anyway -- the SC_GEMM_F16 contraction (engine.mode_gemm) reading xhat or g_yhat -- or where
+    the producer's values are float16 already (that contraction's yhat and g_xhat); then no value changes."""
+    group = group if group is not None else get_model_parallel_group()
+    return _AllToAllC32.apply(x, int(k1), int(w0), int(rows), bool(to_rows), group)
+
+
 # ---- halo exchange of a row-sharded tensor (the skip-path resample of mpu.SpatialParallelSpectralConv) ------------
 def _row_splits(h, ranges, p):
     """[(a, b)] per peer q: the rows of rank p's shard [p h, (p + 1) h) inside peer q's range, local indices"""

@@ -314,13 +314,21 @@ class ModeParallelSpectralConv(BaseSpectralConv):
     REPLICATED, the factor (TT: core) of the first mode dim is sharded by rows like the dense weight; a rank contracts
     with the dense block rebuilt from its shard (1 / P of the reconstruction work), the gradients of the replicated
     parameters are partial sums over this rank's modes and are summed over the group by ``reduce_replicated_grads``.
-    (Round 3: CP, TT and separable joined dense and Tucker.)"""
+    (Round 3: CP, TT and separable joined dense and Tucker.)
+
+    ``fno_block_precision`` "half" / "mixed" follows SpectralConv.forward: real data on an unchanged grid with a
+    not-separable weight takes ``_forward_half`` (SpectralConv._forward_half's cast points, the four exchanges on the
+    complex32 wire of mappings.all_to_all_c32); a separable weight or a change of grid computes in fp32 with the same
+    output dtype rule."""
 
     def __init__(self, in_channels, out_channels, n_modes, bias=True, init_std="auto",
                  fft_norm="forward", device=None, engine_flags=0, group=None, ops=None, comm_chunks=None,
                  factorization=None, rank=0.5, separable=False, max_n_modes=None, resolution_scaling_factor=None,
-                 agops=None, chunk_dim=None, emulate_world=1, **unused):
+                 agops=None, chunk_dim=None, emulate_world=1, fno_block_precision="full", **unused):
         super().__init__(device=device)
+        if fno_block_precision not in ("full", "half", "mixed"):
+            raise ValueError(f"fno_block_precision={fno_block_precision!r}: expected full, half or mixed")
+        self.fno_block_precision = fno_block_precision
         # complex_data (spectral_convolution.py:439-441, 475-479, 514-517, 536-538): complex-to-complex transforms in every
         # dim, every dim centred -- runs on the general route (round 4)
         self.complex_data = bool(unused.pop("complex_data", False))
@@ -465,6 +473,18 @@ class ModeParallelSpectralConv(BaseSpectralConv):
         if x.shape[1] != self.in_channels:
             raise ValueError(f"input has {x.shape[1]} channels, the layer expects {self.in_channels}")
         out_shape = self._out_shape(spatial, output_shape)
+        if self.fno_block_precision in ("half", "mixed") and not self.complex_data:
+            # SpectralConv.forward's rule: the float16 arithmetic on an unchanged grid with a not-separable weight,
+            # fp32 arithmetic and the same output dtype otherwise
+            x = x.float()
+            if not self.separable and out_shape == spatial:
+                kept, w_start = kept_block(spatial, self._n_modes, self.max_n_modes)
+                return self._forward_half(x, spatial, kept, w_start)
+            y = self._forward_fp32(x, spatial, out_shape)
+            return y if self.bias is not None else y.half()      # half + fp32 bias promotes to fp32 upstream
+        return self._forward_fp32(x, spatial, out_shape)
+
+    def _forward_fp32(self, x, spatial, out_shape):
         if self.complex_data:
             from ..modes import kept_block_complex
             kept, w_start = kept_block_complex(spatial, self._n_modes, self.max_n_modes)
@@ -513,6 +533,34 @@ class ModeParallelSpectralConv(BaseSpectralConv):
             y = ag.inverse_transform(yhat, None, out_shape, fs)
             return y if self.bias is None else y + self.bias
         return ag.inverse_transform(yhat, self.bias, out_shape, fs, real_col)
+
+    def _forward_half(self, x, spatial, kept, w_start):
+        """``fno_block_precision`` "half" / "mixed" at the cast points of SpectralConv._forward_half: x rounded to float16
+        ("half"), the SC_GEMM_F16 contraction of this rank's mode rows (both operands and the result rounded to float16,
+        the gradients likewise), the inverse transform rounded to float16, then the bias (none: a float16 result).  The
+        four spectra that cross the group -- xhat and yhat here, g_yhat and g_xhat in the backward -- are float16 values
+        where they are read, so they travel as complex32 (mappings.all_to_all_c32: half the bytes of the fp32 wire).
+        The general route's layout: kept row r rides on stored weight row w_start[0] + r, owned by rank
+        (w_start[0] + r) // rows.  Runs with any process group, a one-rank group included."""
+        from .. import _lib, engine
+        from .mappings import all_to_all_c32
+        ag = self._agops
+        if ag is None:
+            ag = self._agops = engine.EngineOps(self.fft_norm, self.engine_flags)
+        rows, grp = self.rows, self._group()
+        if self.fno_block_precision == "half":
+            x = engine.round_f16(x)                                                     # spectral_convolution.py:436-437
+        xhat = ag.forward_transform(x, kept)                                            # (n, Cin, k1', rest')
+        xloc = all_to_all_c32(xhat, kept[0], w_start[0], rows, True, grp)              # (P n, Cin, rows, rest')
+        w = self._dense_block()
+        cols = tuple(slice(s0, s0 + k) for s0, k in zip(w_start[1:], kept[1:]))
+        w = w[(slice(None),) * 3 + cols]                                                # sub-block columns
+        pn, ci, co = int(xloc.shape[0]), int(w.shape[0]), int(w.shape[1])
+        m = rows * math.prod(kept[1:])
+        yloc = engine.mode_gemm(xloc.reshape(pn, ci, m), w.reshape(ci, co, m), m, flags=_lib.SC_GEMM_F16)
+        yhat = all_to_all_c32(yloc.reshape(pn, co, rows, *kept[1:]), kept[0], w_start[0], rows, False, grp)
+        y = engine.round_f16(ag.inverse_transform(yhat, None, spatial))
+        return y + self.bias if self.bias is not None else y.half()
 
     def _dense_block(self):
         """this rank's (Cin, Cout, rows, ...) block -- (C, rows, ...) when separable -- with autograd to the parameters"""

@@ -82,8 +82,11 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
 
     def __init__(self, in_channels, out_channels, n_modes, bias=True, init_std="auto",
                  fft_norm="forward", device=None, engine_flags=0, group=None, ops=None, factorization=None, rank=0.5,
-                 fixed_rank_modes=None, resolution_scaling_factor=None, **unused):
+                 fixed_rank_modes=None, resolution_scaling_factor=None, fno_block_precision="full", **unused):
         super().__init__(device=device)
+        if fno_block_precision not in ("full", "half", "mixed"):
+            raise ValueError(f"fno_block_precision={fno_block_precision!r}: expected full, half or mixed")
+        self.fno_block_precision = fno_block_precision
         self.separable = bool(unused.get("separable", False))          # spectral_convolution.py:123-131, 49-52
         if self.separable and in_channels != out_channels:
             raise ValueError("To use separable Fourier Conv, in_channels must be equal to out_channels, "
@@ -244,11 +247,27 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
         return out
 
     def forward(self, x, output_shape=None):
-        """``output_shape``: the FULL output grid (all ranks pass the same one); this rank returns its rows of it."""
+        """``output_shape``: the FULL output grid (all ranks pass the same one); this rank returns its rows of it.
+
+        ``fno_block_precision`` "half" / "mixed" follows SpectralConv.forward: on an unchanged grid with a not-separable
+        weight, x rounded to float16 ("half"), the SC_GEMM_F16 contraction of this rank's mode columns and the inverse
+        transform rounded to float16 before the bias (none: a float16 result) -- SpectralConv._forward_half's cast
+        points; a separable weight or a change of grid: fp32 arithmetic, the same output dtype.  The two exchanges stay
+        fp32: they carry half-transformed data, not float16 values."""
         if x.ndim != self.order + 2:
             raise ValueError(f"expected a (B, C, {self.order} spatial dims) input, got {tuple(x.shape)}")
         if x.is_complex() != self.complex_data:
             raise ValueError("complex_data=True takes complex inputs (and only those)")
+        if self.fno_block_precision in ("half", "mixed") and not self.complex_data:
+            x = x.float()
+            in_grid = [x.shape[2] * self.P] + list(x.shape[3:])
+            if not self.separable and self._out_grid(in_grid, output_shape) == in_grid:
+                return self._forward(x, output_shape, half=True)
+            y = self._forward(x, output_shape)
+            return y if self.bias is not None else y.half()      # half + fp32 bias promotes to fp32 upstream
+        return self._forward(x, output_shape)
+
+    def _forward(self, x, output_shape, half=False):
         cplx = self.complex_data
         b, c, h_loc = x.shape[:3]
         rest = list(x.shape[3:])
@@ -263,6 +282,9 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
         fa = analysis_freqs(in_grid, kept, cplx)
         fs, real_col = synthesis_freqs(in_grid, out_grid, kept, cplx)
         d1_o, rest_o, h_out = out_grid[0], out_grid[1:], out_grid[0] // self.P
+        if half and self.fno_block_precision == "half":
+            from .. import engine
+            x = engine.round_f16(x)                                                     # spectral_convolution.py:436-437
         # 1. local rows: pruned transform over d2..dN (rows folded into the channel count)
         xr = x.reshape(b, c * h_loc, *rest)
         xh = self.ops.forward_transform(xr, kept[1:]) if fa is None else self.ops.forward_transform(xr, kept[1:], fa[1:])
@@ -279,7 +301,13 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
         xa = xa.reshape(*lead, k1).movedim(-1, 2).contiguous()                   # (B, Cin, k1, k2p/P, ..)
         # 4. contraction with this rank's mode columns
         wl = self._local_weight(kept, w_start).contiguous()
-        yh = self.ops.contract_separable(xa, wl) if self.separable else self.ops.contract(xa, wl)   # (B, Cout, k1, k2p/P, ..)
+        if half:                          # the complex-half contraction (SC_GEMM_F16), forward and gradients
+            from .. import _lib, engine
+            m = int(np.prod(xa.shape[2:]))
+            yh = engine.mode_gemm(xa.reshape(b, c, m), wl.reshape(c, co, m), m,
+                                  flags=_lib.SC_GEMM_F16).reshape(b, co, *xa.shape[2:])
+        else:
+            yh = self.ops.contract_separable(xa, wl) if self.separable else self.ops.contract(xa, wl)   # (B, Cout, k1, k2p/P, ..)
         # 5. zero-padded inverse DFT over d1 (to the OUTPUT grid's rows)
         yt = yh.movedim(2, -1).contiguous()
         lead = yt.shape[:-1]
@@ -303,6 +331,10 @@ class SpatialParallelSpectralConv(BaseSpectralConv):
         if cplx:                          # a real bias added to a complex field: elementwise glue (:567-568)
             y = self.ops.inverse_transform(ya, None, rest_o, fl).reshape(b, co, h_out, *rest_o)
             return y if self.bias is None else y + self.bias
+        if half:                          # float16(inverse transform), then the bias (SpectralConv._forward_half)
+            from .. import engine
+            y = engine.round_f16(self.ops.inverse_transform(ya, None, rest_o)).reshape(b, co, h_out, *rest_o)
+            return y + self.bias if self.bias is not None else y.half()
         bias = None
         if self.bias is not None:
             bias = self.bias.reshape(co, 1).expand(co, h_out).reshape(co * h_out, *(1,) * len(rest))
