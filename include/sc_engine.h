@@ -262,6 +262,20 @@ int sc_bicubic_rows_forward(const float* x, float* y, int64_t images, int64_t ro
 int sc_bicubic_rows_backward(const float* gy, float* gx, int64_t images, int64_t rows_in, int64_t w_in, int64_t src_row0,
                              int64_t h_in, int64_t h_out, int64_t w_out, int64_t out_row0, int64_t rows_out, void* stream);
 
+/* ---- Legendre (latitude) stage of the real spherical-harmonic transforms ----
+ * Replaces the two einsums of torch_harmonics' RealSHT / InverseRealSHT that neuralop/layers/spherical_convolution.py
+ * calls through its SHT wrapper (:206-281, SphericalConv.forward :430-472):
+ *   analysis   c[line, l, m] = sum_k x[line, k, m] tab[l, k, m]    x (lines, nlat, mmax), c (lines, lmax, mmax)
+ *   synthesis  x[line, k, m] = sum_l c[line, l, m] tab[l, k, m]    c (lines, lmax, mmax), x (lines, nlat, mmax)
+ * Operands complex64 interleaved and contiguous (x is the output of a 1-d real sc_transform_forward plan read in place,
+ * resp. the input of its inverse); tab a REAL fp32 table (lmax, nlat, mmax), zero for l < m: those terms are skipped,
+ * not read.  The output is overwritten in full (zeros at l < m in c).  With a real table the two calls are each
+ * other's adjoint (the autograd of one is the other with the same table).  Deterministic: no atomics. */
+int sc_legendre_analysis(const float* x, const float* tab, float* c, int64_t lines, int64_t nlat, int64_t lmax,
+                         int64_t mmax, void* stream);
+int sc_legendre_synthesis(const float* c, const float* tab, float* x, int64_t lines, int64_t nlat, int64_t lmax,
+                          int64_t mmax, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

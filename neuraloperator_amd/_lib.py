@@ -171,7 +171,7 @@ class ScEngineLib:
                "sc_peer_window_close", "sc_peer_window_free", "sc_peer_all_to_all", "sc_peer_window_control", "sc_pointwise_linear_forward_ex",
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
                "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
-               "sc_wire_pack_c32", "sc_wire_unpack_c32"]
+               "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -316,6 +316,9 @@ class ScEngineLib:
         L.sc_round_f16.restype = c_int
         for s in ("sc_bicubic_rows_forward", "sc_bicubic_rows_backward"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 9 + [c_void_p]
+            getattr(L, s).restype = c_int
+        for s in ("sc_legendre_analysis", "sc_legendre_synthesis"):
+            getattr(L, s).argtypes = [c_void_p, c_void_p, c_void_p] + [c_int64] * 4 + [c_void_p]
             getattr(L, s).restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
@@ -597,6 +600,14 @@ class ScEngineLib:
         """gx (images, rows_in, w_in) overwritten with the adjoint of bicubic_rows_forward applied to gy"""
         self._check(self.lib.sc_bicubic_rows_backward(gy_ptr, gx_ptr, images, rows_in, w_in, src_row0, h_in, h_out,
                                                       w_out, out_row0, rows_out, stream))
+
+    def legendre_analysis(self, x_ptr, tab_ptr, c_ptr, lines, nlat, lmax, mmax, stream=0):
+        """c (lines, lmax, mmax) = sum over k of x (lines, nlat, mmax) times the real table (lmax, nlat, mmax)"""
+        self._check(self.lib.sc_legendre_analysis(x_ptr, tab_ptr, c_ptr, lines, nlat, lmax, mmax, stream))
+
+    def legendre_synthesis(self, c_ptr, tab_ptr, x_ptr, lines, nlat, lmax, mmax, stream=0):
+        """x (lines, nlat, mmax) = sum over l of c (lines, lmax, mmax) times the real table (lmax, nlat, mmax)"""
+        self._check(self.lib.sc_legendre_synthesis(c_ptr, tab_ptr, x_ptr, lines, nlat, lmax, mmax, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

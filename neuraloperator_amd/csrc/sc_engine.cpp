@@ -43,6 +43,7 @@
 #include "sc_kernels_tkchain.h"
 #include "sc_kernels_peer.h"
 #include "sc_kernels_bicubic.h"
+#include "sc_kernels_sht.h"
 #include "sc_kernels_wire.h"
 
 // ------------------------------------------------------------------------------------------
@@ -3486,6 +3487,41 @@ extern "C" int sc_bicubic_rows_backward(const float* gy, float* gx, int64_t imag
               gy + i0 * rows_out * w_out, gx + i0 * rows_in * w_in, g);
   }
   return sc_check_launch("k_bicubic_rows_bwd");
+}
+
+// ---- Legendre stage of the real spherical-harmonic transforms (sc_kernels_sht.h) ------------------------------
+static int sc_legendre_launch(bool synthesis, const float* in, const float* tab, float* out, int64_t lines,
+                              int64_t nlat, int64_t lmax, int64_t mmax, void* stream) {
+  SC_CHECK_ARG(lines >= 0 && nlat > 0 && lmax > 0 && mmax > 0, "legendre: empty transform");
+  SC_CHECK_ARG(nlat < (1 << 20) && lmax < (1 << 20) && mmax < (1 << 20) && lmax * nlat * mmax < ((int64_t)1 << 31),
+               "legendre: table above 2^31 entries");
+  SC_CHECK_ARG(lines / SHT_LT < ((int64_t)1 << 31) - 1, "legendre: too many lines");
+  if (lines == 0) return 0;
+  SC_CHECK_ARG(in && tab && out, "null argument");
+  LegendreArgs a;
+  a.lines = lines;
+  a.nlat = (int)nlat;
+  a.lmax = (int)lmax;
+  a.mmax = (int)mmax;
+  const int64_t rows = synthesis ? nlat : lmax;
+  const dim3 grid((unsigned)((lines + SHT_LT - 1) / SHT_LT), (unsigned)((rows + SHT_ROWS - 1) / SHT_ROWS),
+                  (unsigned)((mmax + 63) / 64));
+  if (synthesis) {
+    SC_LAUNCH(k_legendre_synthesis, grid, dim3(256), 0, (sc_stream_t)stream, in, tab, out, a);
+    return sc_check_launch("k_legendre_synthesis");
+  }
+  SC_LAUNCH(k_legendre_analysis, grid, dim3(256), 0, (sc_stream_t)stream, in, tab, out, a);
+  return sc_check_launch("k_legendre_analysis");
+}
+
+extern "C" int sc_legendre_analysis(const float* x, const float* tab, float* c, int64_t lines, int64_t nlat,
+                                    int64_t lmax, int64_t mmax, void* stream) {
+  return sc_legendre_launch(false, x, tab, c, lines, nlat, lmax, mmax, stream);
+}
+
+extern "C" int sc_legendre_synthesis(const float* c, const float* tab, float* x, int64_t lines, int64_t nlat,
+                                     int64_t lmax, int64_t mmax, void* stream) {
+  return sc_legendre_launch(true, c, tab, x, lines, nlat, lmax, mmax, stream);
 }
 
 extern "C" int sc_modegemm_path(const sc_modegemm_desc* d) {

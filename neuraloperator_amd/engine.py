@@ -794,6 +794,77 @@ class BicubicRowsFn(torch.autograd.Function):
         return gx, None, None, None, None, None
 
 
+def _legendre(which, src, tab, rows):
+    """one sc_legendre_analysis / _synthesis call: src (lines, Q, mmax) complex64, tab (lmax, nlat, mmax) float32 ->
+    (lines, rows, mmax) complex64.  Both pointers reach the kernel: both tensors must be on the same GPU (a host table
+    would be read by the device)."""
+    _require_gpu(src, "Legendre operand")
+    _require_gpu(tab, "Legendre table")
+    if tab.device != src.device:
+        raise ValueError(f"Legendre table on {tab.device}, operand on {src.device}: move the transform with "
+                         ".to(device) first")
+    src = src if src.dtype == torch.complex64 else src.to(torch.complex64)
+    src = src.resolve_conj().contiguous()              # autograd hands lazily conjugated gradients on
+    lines, _, mmax = (int(v) for v in src.shape)
+    lmax, nlat = int(tab.shape[0]), int(tab.shape[1])
+    out = torch.empty((lines, int(rows), mmax), dtype=torch.complex64, device=src.device)
+    with torch.cuda.device(src.device):
+        getattr(_lib.get_lib(), "legendre_" + which)(torch.view_as_real(src).data_ptr(), tab.data_ptr(),
+                                                     torch.view_as_real(out).data_ptr(), lines, nlat, lmax, mmax,
+                                                     _stream())
+    return out
+
+
+def _legendre_table(tab, lmax, nlat, mmax):
+    if tab.dtype != torch.float32 or tuple(tab.shape) != (lmax, nlat, mmax) or not tab.is_contiguous():
+        raise ValueError(f"Legendre table: a contiguous float32 ({lmax}, {nlat}, {mmax}) tensor, got "
+                         f"{tuple(tab.shape)} {tab.dtype}")
+    return tab
+
+
+class LegendreAnalysisFn(torch.autograd.Function):
+    """c[line, l, m] = sum_k x[line, k, m] tab[l, k, m] (sc_legendre_analysis): the latitude stage of RealSHT, x the
+    (lines, nlat, mmax) output of the longitude transform, tab real.  The gradient is the synthesis kernel with the SAME
+    table (tab is real: no conjugation); the table gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, tab):
+        _require_gpu(x, "x")
+        if x.dim() != 3 or tab.dim() != 3:
+            raise ValueError(f"Legendre analysis: x (lines, nlat, mmax) and tab (lmax, nlat, mmax), got "
+                             f"{tuple(x.shape)} and {tuple(tab.shape)}")
+        lmax = int(tab.shape[0])
+        _legendre_table(tab, lmax, int(x.shape[1]), int(x.shape[2]))
+        ctx.save_for_backward(tab)
+        return _legendre("analysis", x, tab, lmax)
+
+    @staticmethod
+    def backward(ctx, gc):
+        tab, = ctx.saved_tensors
+        return _legendre("synthesis", gc, tab, int(tab.shape[1])), None
+
+
+class LegendreSynthesisFn(torch.autograd.Function):
+    """x[line, k, m] = sum_l c[line, l, m] tab[l, k, m] (sc_legendre_synthesis): the latitude stage of InverseRealSHT,
+    c (lines, lmax, mmax).  The gradient is the analysis kernel with the same table."""
+
+    @staticmethod
+    def forward(ctx, c, tab):
+        _require_gpu(c, "c")
+        if c.dim() != 3 or tab.dim() != 3:
+            raise ValueError(f"Legendre synthesis: c (lines, lmax, mmax) and tab (lmax, nlat, mmax), got "
+                             f"{tuple(c.shape)} and {tuple(tab.shape)}")
+        nlat = int(tab.shape[1])
+        _legendre_table(tab, int(c.shape[1]), nlat, int(c.shape[2]))
+        ctx.save_for_backward(tab)
+        return _legendre("synthesis", c, tab, nlat)
+
+    @staticmethod
+    def backward(ctx, gx):
+        tab, = ctx.saved_tensors
+        return _legendre("analysis", gx, tab, int(tab.shape[0])), None
+
+
 class EngineOps:
     """The three local stages of a (mode-parallel) spectral layer on the MI355X engine."""
 
@@ -817,6 +888,16 @@ class EngineOps:
         for k in xhat.shape[2:]:
             m *= int(k)
         return mode_gemm(xhat.reshape(b, 1, m), w.reshape(1, 1, m), m).reshape(xhat.shape)
+
+    # the latitude stage of the spherical-harmonic transforms (harmonics.RealSHT / InverseRealSHT): x (lines, nlat,
+    # mmax) <-> c (lines, lmax, mmax) against a real (lmax, nlat, mmax) table
+    @staticmethod
+    def legendre_analysis(x, tab):
+        return LegendreAnalysisFn.apply(x, tab)
+
+    @staticmethod
+    def legendre_synthesis(c, tab):
+        return LegendreSynthesisFn.apply(c, tab)
 
     # one complex axis of a separable transform (the sharded dim of mpu.SpatialParallelSpectralConv):
     # x (B, L, n) complex -> (B, L, k) with kept row r reading FFT index rows[r], and its zero-padded inverse;

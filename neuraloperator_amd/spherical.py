@@ -16,8 +16,9 @@ with Clenshaw-Curtis nodes / weights on the "equiangular" grid (both poles inclu
 itself is UNPINNED (it cannot be imported here); the tables are pinned against scipy's spherical harmonics and numpy's
 Gauss-Legendre rule, the transforms by their defining properties (tests/test_spherical.py).
 
-On the engine: the longitude transforms are 1-d plans (k_last_r2c / k_last_c2r families, sc_transform_forward /
-_inverse), the two Legendre transforms and the channel contraction are sc_modegemm launches (modes = m, resp. = l),
+On the engine: the transforms are harmonics.RealSHT / InverseRealSHT -- the longitude stage 1-d plans (k_last_r2c /
+k_last_c2r families, sc_transform_forward / _inverse), the latitude stage the Legendre kernels of sc_kernels_sht.h
+against real tables (sc_legendre_analysis / _synthesis); the channel contraction is an sc_modegemm launch (modes = l),
 autograd through the same Functions as the planar layer.  Constructor, attributes and ``forward`` / ``transform``
 follow the reference class."""
 import math
@@ -94,59 +95,33 @@ def legendre_table(mmax, lmax, theta, norm="ortho", inverse=False):
 
 
 class SHT(nn.Module):
-    """Spherical-harmonic transforms with the call interface of the reference's wrapper (:206-281), on the engine."""
+    """Spherical-harmonic transforms with the call interface of the reference's wrapper (:206-281), on the engine:
+    cached harmonics.RealSHT / InverseRealSHT per (grid, modes, norm, device), as the wrapper caches torch_harmonics'."""
 
     def __init__(self, dtype=torch.float32, device=None, engine_flags=0):
         super().__init__()
         self.device, self.dtype, self.flags = device, dtype, engine_flags
         self._tab = {}
 
-    def _table(self, key, build, dev):
-        k = (key, str(dev))
+    def _transform(self, cls, nlat, nlon, lmax, mmax, norm, grid, dev):
+        k = (cls.__name__, nlat, nlon, lmax, mmax, norm, grid, str(dev))
         if k not in self._tab:
-            t = torch.from_numpy(np.ascontiguousarray(build())).to(torch.float32)
-            self._tab[k] = torch.complex(t, torch.zeros_like(t)).to(dev).contiguous()
+            t = cls(nlat, nlon, lmax=lmax, mmax=mmax, grid=grid, norm=norm).to(dev)
+            t._engine_flags = self.flags                     # the layer's engine_flags reach the 1-d plans
+            self._tab[k] = t
         return self._tab[k]
 
     def sht(self, x, s=None, norm="ortho", grid="equiangular"):
-        *lead, nlat, nlon = x.shape
+        from .harmonics import RealSHT
+        *_, nlat, nlon = x.shape
         lmax, mmax = (nlat, nlat // 2 if grid == "equiangular" else nlat) if s is None else (int(s[0]), int(s[1]))
-        if mmax > nlon // 2 + 1:
-            raise ValueError(f"mmax = {mmax} exceeds the {nlon // 2 + 1} longitudinal modes of {nlon} points")
-
-        def build():
-            theta, w = quadrature(nlat, grid)
-            return (legendre_table(mmax, lmax, theta, norm) * w[None, None, :]).transpose(2, 1, 0)   # [k, l, m]
-
-        wt = self._table(("f", nlat, lmax, mmax, norm, grid), build, x.device)
-        ops = engine.EngineOps("forward", self.flags)
-        n_lines = 1
-        for v in lead:
-            n_lines *= int(v)
-        xh = ops.forward_transform(x.reshape(1, n_lines * nlat, nlon), [mmax])           # rfft / nlon, mmax columns
-        xh = xh.reshape(n_lines, nlat, mmax) * (2.0 * math.pi)
-        out = engine.mode_gemm(xh, wt, mmax)                                              # [lines, lmax, mmax]
-        return out.reshape(*lead, lmax, mmax)
+        return self._transform(RealSHT, nlat, nlon, lmax, mmax, norm, grid, x.device)(x)
 
     def isht(self, x, s=None, norm="ortho", grid="equiangular"):
-        *lead, lmax, mmax = x.shape
+        from .harmonics import InverseRealSHT
+        *_, lmax, mmax = x.shape
         nlat, nlon = (lmax, 2 * mmax if grid == "equiangular" else mmax) if s is None else (int(s[0]), int(s[1]))
-
-        def build():
-            theta, _ = quadrature(nlat, grid)
-            return legendre_table(mmax, lmax, theta, norm, inverse=True).transpose(1, 2, 0)            # [l, k, m]
-
-        pt = self._table(("i", nlat, lmax, mmax, norm, grid), build, x.device)
-        n_lines = 1
-        for v in lead:
-            n_lines *= int(v)
-        xh = engine.mode_gemm(x.reshape(n_lines, lmax, mmax).to(torch.complex64), pt, mmax)   # [lines, nlat, mmax]
-        keep = min(mmax, nlon // 2 + 1)                      # irfft(n = nlon) reads the first nlon / 2 + 1 columns only
-        if keep < mmax:
-            xh = xh[..., :keep].contiguous()
-        ops = engine.EngineOps("forward", self.flags)
-        y = ops.inverse_transform(xh.reshape(1, n_lines * nlat, keep), None, [nlon])
-        return y.reshape(*lead, nlat, nlon)
+        return self._transform(InverseRealSHT, nlat, nlon, lmax, mmax, norm, grid, x.device)(x)
 
 
 class SphericalConv(BaseSpectralConv):
