@@ -2200,9 +2200,27 @@ static int run_gemm8(const sc_modegemm_desc* d, const cf32* A, const cf32* B, cf
 // The two contractions of a backward pass (and the bias gradient) as ONE launch of k_modegemm_dma_bwd
 // (sc_kernels_gemm8.h): d0 = weight gradient (conj A), d1 = gradient of the spectrum (conj B).  Returns -1 when the
 // pair does not qualify (the caller then launches them one after the other).
-#ifndef SC_G8_PAIR_BPW                   // measurement builds: 0 = as chosen per job, 1 = all tiles of a mode group in
+#ifndef SC_G8_PAIR_BPW                   // measurement builds: 0 = one tile per workgroup, 1 = all tiles of a mode group in
 #define SC_G8_PAIR_BPW 0                 // one workgroup (both jobs), 2 = that for the weight gradient only
 #endif
+// geometry of the two jobs of k_modegemm_dma_bwd: the narrow shape, ONE tile per workgroup (the kernel puts the job
+// with the longer workgroups first: many short workgroups at the end of the launch balance the CUs better than a
+// second round of tiles run back to back; profiles/r07_pair_schedule_ab.txt)
+static void gemm8_pair_args(const sc_modegemm_desc* d0, const sc_modegemm_desc* d1, Gemm8Args& g0, Gemm8Args& g1) {
+  gemm8_args(d0, g0, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
+  gemm8_args(d1, g1, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
+  for (Gemm8Args* g : {&g0, &g1}) {
+    g->bpw = 1;
+    g->G = (int)((int64_t)g->n_mg * g->n_pb * g->n_qb);
+  }
+#if SC_G8_PAIR_BPW >= 1
+  g0.bpw = g0.n_pb * g0.n_qb; g0.G = g0.n_mg;
+#endif
+#if SC_G8_PAIR_BPW == 1
+  g1.bpw = g1.n_pb * g1.n_qb; g1.G = g1.n_mg;
+#endif
+}
+
 static int run_gemm8_bwd(const sc_modegemm_desc* d0, const cf32* A0, const cf32* B0, cf32* C0,
                          const sc_modegemm_desc* d1, const cf32* A1, const cf32* B1, cf32* C1,
                          const Gemm8Bias& bias, sc_stream_t st) {
@@ -2219,15 +2237,8 @@ static int run_gemm8_bwd(const sc_modegemm_desc* d0, const cf32* A0, const cf32*
   if (gemm8_args(d0, g0, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), -1) ||
       gemm8_args(d1, g1, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), -1)) return -1;
 #endif
-  gemm8_args(d0, g0, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
-  gemm8_args(d1, g1, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
-#if SC_G8_PAIR_BPW >= 1
-  g0.bpw = g0.n_pb * g0.n_qb; g0.G = g0.n_mg;
-#endif
-#if SC_G8_PAIR_BPW == 1
-  g1.bpw = g1.n_pb * g1.n_qb; g1.G = g1.n_mg;
-#endif
-  if ((g0.G & 7) || (g1.G & 7)) return -1;                    // octets of workgroups alternate between the jobs
+  gemm8_pair_args(d0, d1, g0, g1);
+  if ((g0.G & 7) || (g1.G & 7)) return -1;                    // the jobs are laid out in octets of workgroups
   typedef Gemm8Cfg<4, 2, 2> K;
   const int64_t nb = bias.ghat ? (bias.channels + K::NW - 1) / K::NW : 0;
   if ((int64_t)g0.G + g1.G + nb >= ((int64_t)1 << 30)) return -1;
@@ -2323,14 +2334,7 @@ extern "C" int sc_modegemm_pair_fused(const sc_modegemm_desc* d0, const sc_modeg
   if (!gemm8_eligible(d0, al, al, al) || !gemm8_eligible(d1, al, al, al)) return 0;
   if (!(d0->conj_a && !d0->conj_b && !d1->conj_a && d1->conj_b) || d0->n_modes != d1->n_modes) return 0;
   Gemm8Args g0, g1;
-  gemm8_args(d0, g0, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
-  gemm8_args(d1, g1, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), 0);
-#if SC_G8_PAIR_BPW >= 1
-  g0.G = g0.n_mg;
-#endif
-#if SC_G8_PAIR_BPW == 1
-  g1.G = g1.n_mg;
-#endif
+  gemm8_pair_args(d0, d1, g0, g1);
   return !((g0.G & 7) || (g1.G & 7));
 #endif
 }

@@ -500,8 +500,13 @@ k_modegemm_dma(Gemm8Args g, const cf32* __restrict__ A, const cf32* __restrict__
 // the average is 2.06, and the launch is as slow as its busiest CU (profiles/r02_gemm_dma_v4_grid_scaling.txt:
 // 512 / 528 / 1024 workgroups take 35.9 / 43.6 / 68.8 us).  Together the two jobs are 1056 workgroups: the second
 // round of the one fills the tail of the other, both read ghat while it is in the Infinity Cache, and two launch
-// boundaries disappear.  Octets of consecutive workgroups (one per XCD) alternate between the jobs, so inside each
-// job workgroup k still runs on XCD k % 8 and g8_workgroup's XCD-aware unit order holds.
+// boundaries disappear.  Every workgroup takes ONE tile (bpw = 1: the metric shape's weight gradient is 1056 workgroups
+// of 8 stages, its spectrum gradient 528 of 16) and the job with the longer workgroups comes first, so the launch ends
+// on short workgroups spread over the CUs that free up first instead of a second round of long ones (round 7: pair
+// 67.5 -> 61.1 us, profiles/r07_pair_schedule_ab.txt).  Jobs are laid out in octets of consecutive workgroups (one per
+// XCD), so inside each job workgroup k still runs on XCD k % 8 and g8_workgroup's XCD-aware unit order holds.  A
+// tile's r loop, and thus every output's summation order, is the same whatever the grid: the pair gives the bits of
+// the two single launches.
 // ------------------------------------------------------------------------------------------
 struct Gemm8Bias {
   const cf32* ghat;      // null: no bias role
@@ -518,13 +523,14 @@ k_modegemm_dma_bwd(Gemm8Args g0, const cf32* __restrict__ A0, const cf32* __rest
   SC_SHARED __attribute__((aligned(16))) sc_f4 lds[D * K::STAGE_G];
   const int b = SC_BID_X;
   const int n0 = g0.G >> 3, n1 = g1.G >> 3;                 // octets of each job (the host passes G % 8 == 0)
-  const int nmin = n0 < n1 ? n0 : n1;
   const int oct = b >> 3, l8 = b & 7;
   if (oct < n0 + n1) {
-    // octets alternate between the jobs while both have some left; the longer job takes the rest
-    const bool alt = oct < 2 * nmin;
-    const int job = alt ? (oct & 1) : (n1 > n0 ? 1 : 0);
-    const int k = (alt ? (oct >> 1) : (oct - nmin)) * 8 + l8;
+    // the job with more stages per workgroup takes the first octets, the other the rest: the dispatcher hands out
+    // workgroups in order, so the short ones come last and fill the CUs that free up first (profiles/r07_pair_schedule_ab.txt)
+    const int len0 = ((g0.R + 2 * SUB - 1) / (2 * SUB)) * g0.bpw, len1 = ((g1.R + 2 * SUB - 1) / (2 * SUB)) * g1.bpw;
+    const int first = len1 > len0 ? 1 : 0, nf = first ? n1 : n0;
+    const int job = oct < nf ? first : 1 - first;
+    const int k = (oct < nf ? oct : oct - nf) * 8 + l8;
     if (job) g8_workgroup<GS, QT, SUB, D, IL, false, true>(g1, A1, B1, C1, k, lds);
     else g8_workgroup<GS, QT, SUB, D, IL, true, false>(g0, A0, B0, C0, k, lds);
   } else {
