@@ -276,6 +276,37 @@ int sc_legendre_analysis(const float* x, const float* tab, float* c, int64_t lin
 int sc_legendre_synthesis(const float* c, const float* tab, float* x, int64_t lines, int64_t nlat, int64_t lmax,
                           int64_t mmax, void* stream);
 
+/* ---- spectral-derivative multiplier pass ----
+ * The step between the two transforms of neuralop/losses/differentiation.py's FourierDiff (:1167-1345): every
+ * requested derivative spectrum from ONE read of the source spectra, the multipliers formed from per-axis tables:
+ *   yhat[g, t, m] = sum over terms j with term_out[j] = t of
+ *                   term_coef[j] * 1/2 (prod_d A[d][term_tab[j][d]][i_d(m)] + prod_d B[d][term_tab[j][d]][i_d(m)])
+ *                   * xhat[g, term_src[j], m]
+ * xhat (groups, n_src, kept[0..ndim-1]) complex64 contiguous: the output of a full-spectrum SC_FWD_SCALED plan in the
+ * plan's row order.  yhat element (g, t, m) lies at complex offset g * y_group_stride + t * y_out_stride + m (m the
+ * flattened contiguous mode index), so the caller lays the outputs out as (n_out, groups, ..) or (groups, n_out, ..).
+ * A[d], B[d]: device tables [n_tab[d]][kept[d]] complex64 in the same row order.  conj != 0 conjugates both products
+ * (with a Hermitian multiplier that is the adjoint: the backward pass is this call with src / out exchanged and conj).
+ * Every addressed yhat element is overwritten; an output without a term is written as zeros.  At most
+ * SC_SPECOP_MAX_TERMS terms plus term-less outputs (and as many outputs): longer lists are split by the
+ * caller.  8-byte alignment of xhat / yhat suffices.  Deterministic: no atomics. */
+#define SC_SPECOP_MAX_TERMS 12
+typedef struct {
+  int32_t ndim;                               /* 1..3 mode dims                                            */
+  int32_t n_src, n_out, n_terms;              /* n_src <= 3                                                */
+  int32_t conj, reserved;
+  int64_t kept[3];
+  int64_t groups;
+  int64_t y_group_stride, y_out_stride;       /* complex elements                                          */
+  int32_t n_tab[3];
+  int32_t term_src[SC_SPECOP_MAX_TERMS], term_out[SC_SPECOP_MAX_TERMS];
+  int32_t term_tab[SC_SPECOP_MAX_TERMS][3];
+  float term_coef[SC_SPECOP_MAX_TERMS];
+  const float* A[3];
+  const float* B[3];
+} sc_specop_desc;
+int sc_spectral_op(const sc_specop_desc* desc, const float* xhat, float* yhat, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -113,6 +113,18 @@ class PmlpDesc(Structure):
                 ("act", c_int32), ("reserved", c_int32)]
 
 
+SC_SPECOP_MAX_TERMS = 12
+
+
+class SpecopDesc(Structure):                                # sc_specop_desc
+    _fields_ = [("ndim", c_int32), ("n_src", c_int32), ("n_out", c_int32), ("n_terms", c_int32),
+                ("conj", c_int32), ("reserved", c_int32), ("kept", c_int64 * 3), ("groups", c_int64),
+                ("y_group_stride", c_int64), ("y_out_stride", c_int64), ("n_tab", c_int32 * 3),
+                ("term_src", c_int32 * SC_SPECOP_MAX_TERMS), ("term_out", c_int32 * SC_SPECOP_MAX_TERMS),
+                ("term_tab", (c_int32 * 3) * SC_SPECOP_MAX_TERMS), ("term_coef", ctypes.c_float * SC_SPECOP_MAX_TERMS),
+                ("A", c_void_p * 3), ("B", c_void_p * 3)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -171,7 +183,7 @@ class ScEngineLib:
                "sc_peer_window_close", "sc_peer_window_free", "sc_peer_all_to_all", "sc_peer_window_control", "sc_pointwise_linear_forward_ex",
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
                "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
-               "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis"]
+               "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -320,6 +332,8 @@ class ScEngineLib:
         for s in ("sc_legendre_analysis", "sc_legendre_synthesis"):
             getattr(L, s).argtypes = [c_void_p, c_void_p, c_void_p] + [c_int64] * 4 + [c_void_p]
             getattr(L, s).restype = c_int
+        L.sc_spectral_op.argtypes = [POINTER(SpecopDesc), c_void_p, c_void_p, c_void_p]
+        L.sc_spectral_op.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -608,6 +622,26 @@ class ScEngineLib:
     def legendre_synthesis(self, c_ptr, tab_ptr, x_ptr, lines, nlat, lmax, mmax, stream=0):
         """x (lines, nlat, mmax) = sum over l of c (lines, lmax, mmax) times the real table (lmax, nlat, mmax)"""
         self._check(self.lib.sc_legendre_synthesis(c_ptr, tab_ptr, x_ptr, lines, nlat, lmax, mmax, stream))
+
+    def spectral_op(self, x_ptr, y_ptr, *, kept, groups, n_src, n_out, terms, tabs_a, tabs_b, n_tab, y_group_stride,
+                    y_out_stride, conj=False, stream=0):
+        """yhat[g, t] = sum over terms (src, out, coef, tab rows per axis) with out = t of
+        coef * (prod_d A_d[tab_d] + prod_d B_d[tab_d]) / 2 * xhat[g, src] (sc_spectral_op); tabs_a / tabs_b the device
+        pointers of the per-axis tables [n_tab_d][kept_d] complex64"""
+        d = SpecopDesc()
+        nd = len(kept)
+        if len(terms) > SC_SPECOP_MAX_TERMS or not 1 <= nd <= 3:
+            raise EngineError(f"sc_spectral_op: {len(terms)} terms over {nd} dims (at most {SC_SPECOP_MAX_TERMS} terms "
+                              "of 1 to 3 dims per call)")
+        d.ndim, d.n_src, d.n_out, d.n_terms, d.conj = nd, n_src, n_out, len(terms), int(bool(conj))
+        d.groups, d.y_group_stride, d.y_out_stride = groups, y_group_stride, y_out_stride
+        for i in range(nd):
+            d.kept[i], d.n_tab[i], d.A[i], d.B[i] = kept[i], n_tab[i], tabs_a[i], tabs_b[i]
+        for j, (src, out, coef, tab) in enumerate(terms):
+            d.term_src[j], d.term_out[j], d.term_coef[j] = src, out, coef
+            for i in range(nd):
+                d.term_tab[j][i] = tab[i]
+        self._check(self.lib.sc_spectral_op(byref(d), x_ptr, y_ptr, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

@@ -44,6 +44,7 @@
 #include "sc_kernels_peer.h"
 #include "sc_kernels_bicubic.h"
 #include "sc_kernels_sht.h"
+#include "sc_kernels_specop.h"
 #include "sc_kernels_wire.h"
 
 // ------------------------------------------------------------------------------------------
@@ -3526,6 +3527,90 @@ extern "C" int sc_legendre_analysis(const float* x, const float* tab, float* c, 
 extern "C" int sc_legendre_synthesis(const float* c, const float* tab, float* x, int64_t lines, int64_t nlat,
                                      int64_t lmax, int64_t mmax, void* stream) {
   return sc_legendre_launch(true, c, tab, x, lines, nlat, lmax, mmax, stream);
+}
+
+// ---- spectral-derivative multiplier pass (sc_kernels_specop.h) --------------------------------------------------
+extern "C" int sc_spectral_op(const sc_specop_desc* d, const float* xhat, float* yhat, void* stream) {
+  SC_CHECK_ARG(d, "null argument");
+  SC_CHECK_ARG(d->ndim >= 1 && d->ndim <= 3, "spectral_op: ndim must be 1, 2 or 3");
+  SC_CHECK_ARG(d->n_src >= 1 && d->n_src <= SPECOP_MAX_SRC, "spectral_op: 1 to 3 source spectra");
+  SC_CHECK_ARG(d->n_out >= 1 && d->n_out <= SC_SPECOP_MAX_TERMS, "spectral_op: 1 to SC_SPECOP_MAX_TERMS outputs");
+  SC_CHECK_ARG(d->n_terms >= 0 && d->n_terms <= SC_SPECOP_MAX_TERMS,
+               "spectral_op: more than SC_SPECOP_MAX_TERMS terms (split the list into several calls)");
+  SC_CHECK_ARG(d->groups >= 0 && d->groups < ((int64_t)1 << 40), "spectral_op: group count out of range");
+  int64_t rows = 1;
+  for (int i = 0; i < d->ndim; ++i) {
+    SC_CHECK_ARG(d->kept[i] >= 1 && d->kept[i] < (1 << 24), "spectral_op: mode extent out of range");
+    SC_CHECK_ARG(d->n_tab[i] >= 1 && d->n_tab[i] <= 255, "spectral_op: 1 to 255 table rows per axis");
+    if (i < d->ndim - 1) rows *= d->kept[i];
+  }
+  const int64_t kl = d->kept[d->ndim - 1];
+  SC_CHECK_ARG(rows < ((int64_t)1 << 31) - 1 && rows * kl < ((int64_t)1 << 40), "spectral_op: spectrum too large");
+  SC_CHECK_ARG(d->y_group_stride >= 0 && d->y_out_stride >= 0, "spectral_op: negative output stride");
+  for (int j = 0; j < d->n_terms; ++j) {
+    SC_CHECK_ARG(d->term_src[j] >= 0 && d->term_src[j] < d->n_src, "spectral_op: term source out of range");
+    SC_CHECK_ARG(d->term_out[j] >= 0 && d->term_out[j] < d->n_out, "spectral_op: term output out of range");
+    for (int i = 0; i < d->ndim; ++i)
+      SC_CHECK_ARG(d->term_tab[j][i] >= 0 && d->term_tab[j][i] < d->n_tab[i], "spectral_op: table row out of range");
+  }
+  // slots: the terms grouped by output in their given order, plus one zero slot per output without a term
+  SpecopArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int n = 0;
+  for (int t = 0; t < d->n_out; ++t) {
+    const int first = n;
+    int src[SPECOP_SLOTS], tab[SPECOP_SLOTS][3];
+    for (int j = 0; j <= d->n_terms; ++j) {
+      const bool zero = j == d->n_terms;              // after the terms: the zero slot of an output without one
+      if (zero ? n != first : d->term_out[j] != t) continue;
+      SC_CHECK_ARG(n < SPECOP_SLOTS, "spectral_op: terms plus outputs without a term exceed SC_SPECOP_MAX_TERMS (split the call)");
+      a.coef[n] = zero ? 0.f : 0.5f * d->term_coef[j];
+      src[n] = zero ? -1 : d->term_src[j];
+      for (int i = 0; i < 3; ++i) tab[n][i] = 0;
+      if (!zero) {
+        tab[n][0] = d->term_tab[j][d->ndim - 1];
+        for (int i = 0; i < d->ndim - 1; ++i) tab[n][1 + i] = d->term_tab[j][i];
+      }
+      ++n;
+    }
+    for (int k = first; k < n; ++k)
+      a.info[k] = specop_info((k == first ? SPECOP_FIRST : 0) | (k == n - 1 ? SPECOP_LAST : 0), src[k], t, tab[k][0],
+                              tab[k][1], tab[k][2]);
+  }
+  if (d->groups == 0) return 0;
+  SC_CHECK_ARG(xhat && yhat, "null argument");
+  for (int i = 0; i < d->ndim; ++i) SC_CHECK_ARG(d->A[i] && d->B[i], "spectral_op: null table");
+  a.a_last = reinterpret_cast<const cf32*>(d->A[d->ndim - 1]);
+  a.b_last = reinterpret_cast<const cf32*>(d->B[d->ndim - 1]);
+  for (int i = 0; i < d->ndim - 1; ++i) {
+    a.a_row[i] = reinterpret_cast<const cf32*>(d->A[i]);
+    a.b_row[i] = reinterpret_cast<const cf32*>(d->B[i]);
+    a.k_row[i] = (int)d->kept[i];
+  }
+  a.groups = d->groups;
+  a.y_gs = d->y_group_stride;
+  a.y_os = d->y_out_stride;
+  a.n_row_axes = d->ndim - 1;
+  a.kl = (int)kl;
+  a.rows = (int)rows;
+  a.n_src = d->n_src;
+  a.n_slots = n;
+  a.conj = d->conj ? 1 : 0;
+  // waves side by side along the row: 1 up to 128 columns, 2 up to 256, 4 above; the others take different groups
+  a.col_waves_log2 = kl > 256 ? 2 : kl > 128 ? 1 : 0;
+  const int64_t tile = (int64_t)128 << a.col_waves_log2;
+  const int64_t tiles = (kl + tile - 1) / tile;
+  SC_CHECK_ARG(tiles <= 65535, "spectral_op: last mode extent too large");
+  // groups per workgroup: up to 8 (the multipliers are formed once per workgroup) while that leaves 2048 workgroups,
+  // more where the grid limits ask for it
+  int64_t gpw = 8;
+  while (gpw > 1 && rows * tiles * ((d->groups + gpw - 1) / gpw) < 2048) gpw >>= 1;
+  while ((d->groups + gpw - 1) / gpw > 65535 || rows * tiles * ((d->groups + gpw - 1) / gpw) >= ((int64_t)1 << 23))
+    gpw <<= 1;
+  a.gpw = (int)gpw;
+  const dim3 grid((unsigned)rows, (unsigned)tiles, (unsigned)((d->groups + gpw - 1) / gpw));
+  SC_LAUNCH(k_spectral_op, grid, dim3(256), 0, (sc_stream_t)stream, xhat, yhat, a);
+  return sc_check_launch("k_spectral_op");
 }
 
 extern "C" int sc_modegemm_path(const sc_modegemm_desc* d) {

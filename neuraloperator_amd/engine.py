@@ -865,6 +865,127 @@ class LegendreSynthesisFn(torch.autograd.Function):
         return _legendre("analysis", gx, tab, int(tab.shape[0])), None
 
 
+# ---- spectral-derivative multiplier pass (sc_spectral_op) -------------------------------------------------------
+class SpectralTables:
+    """Per-axis multiplier tables of sc_spectral_op on one device: a[d], b[d] complex64 (n_tab_d, kept_d) in the plan's
+    row order (fftshift order on the non-last dims, 0 .. N/2 on the last).  Built once by the caller (float64, rounded
+    once to fp32); constants of the operator, they take no gradient."""
+
+    def __init__(self, a, b):
+        if len(a) != len(b) or not 1 <= len(a) <= 3:
+            raise ValueError("spectral tables: one (a, b) pair per mode dim, 1 to 3 dims")
+        for ta, tb in zip(a, b):
+            if ta.dtype != torch.complex64 or tb.dtype != torch.complex64 or ta.dim() != 2 or ta.shape != tb.shape \
+                    or not (ta.is_contiguous() and tb.is_contiguous()) or ta.device != a[0].device \
+                    or tb.device != a[0].device:
+                raise ValueError("spectral tables: contiguous complex64 (n_tab, kept) pairs on one device")
+        self.a, self.b = list(a), list(b)
+        self.kept = tuple(int(t.shape[1]) for t in a)
+        self.n_tab = tuple(int(t.shape[0]) for t in a)
+        self.device = a[0].device
+
+
+_SPEC_TABLES = collections.OrderedDict()       # (device, key of the caller) -> SpectralTables, least recently used first
+MAX_CACHED_SPEC_TABLES = 256
+
+
+def get_spectral_tables(device, key, build):
+    """Cached device tables, as get_plan caches plans: ``key`` names the operator (grid, L, low-pass ratio, set of
+    orders), ``build()`` returns the host tables (a, b) on a miss."""
+    dev = torch.device(device)
+    full = (dev.type, dev.index if dev.index is not None or dev.type != "cuda" else torch.cuda.current_device(), key)
+    with _PLAN_LOCK:
+        tabs = _SPEC_TABLES.get(full)
+        if tabs is not None:
+            _SPEC_TABLES.move_to_end(full)
+            return tabs
+    a, b = build()
+    tabs = SpectralTables([t.to(dev) for t in a], [t.to(dev) for t in b])
+    with _PLAN_LOCK:
+        _SPEC_TABLES[full] = tabs
+        while len(_SPEC_TABLES) > MAX_CACHED_SPEC_TABLES:
+            _SPEC_TABLES.popitem(last=False)
+    return tabs
+
+
+def _specop_chunks(terms, n_out):
+    """runs of consecutive outputs [t0, t1) whose terms plus term-less outputs fit one launch"""
+    per_out = [sum(1 for t in terms if t[1] == o) for o in range(n_out)]
+    for o, n in enumerate(per_out):
+        if n > _lib.SC_SPECOP_MAX_TERMS:
+            raise ValueError(f"output {o} sums {n} terms; sc_spectral_op takes {_lib.SC_SPECOP_MAX_TERMS} per launch")
+    chunks, t0, used = [], 0, 0
+    for o, n in enumerate(per_out):
+        slots = max(n, 1)
+        if used + slots > _lib.SC_SPECOP_MAX_TERMS:
+            chunks.append((t0, o))
+            t0, used = o, 0
+        used += slots
+    chunks.append((t0, n_out))
+    return chunks
+
+
+def _spectral_op(xhat, tabs, terms, n_out, conj, out_major):
+    """xhat (groups, n_src, *kept) complex64 -> (n_out, groups, *kept) if out_major else (groups, n_out, *kept).
+    terms: tuples (src, out, coef, (table row per dim)).  Lists too long for one launch are split over the outputs; more
+    than three sources (the backward of a many-output call) are summed from launches of three."""
+    _require_gpu(xhat, "spectrum")
+    _require_gpu(tabs.a[0], "spectral tables")
+    if tabs.device != xhat.device:
+        raise ValueError(f"spectral tables on {tabs.device}, spectrum on {xhat.device}")
+    xhat = xhat if xhat.dtype == torch.complex64 else xhat.to(torch.complex64)
+    xhat = xhat.resolve_conj().contiguous()
+    groups, n_src = int(xhat.shape[0]), int(xhat.shape[1])
+    kept = tuple(int(k) for k in xhat.shape[2:])
+    if kept != tabs.kept:
+        raise ValueError(f"spectrum {kept} against tables for {tabs.kept}")
+    for src, out, _, tab in terms:
+        if not (0 <= src < n_src and 0 <= out < n_out and len(tab) == len(kept)
+                and all(0 <= r < n for r, n in zip(tab, tabs.n_tab))):
+            raise ValueError(f"spectral op: term {(src, out, tab)} outside {n_src} sources, {n_out} outputs, "
+                             f"{tabs.n_tab} table rows")
+    if n_src > 3:
+        total = None
+        for s0 in range(0, n_src, 3):
+            part = [(s - s0, o, c, t) for s, o, c, t in terms if s0 <= s < s0 + 3]
+            y = _spectral_op(xhat[:, s0:s0 + 3], tabs, part, n_out, conj, out_major)
+            total = y if total is None else total.add_(y)
+        return total
+    modes = math.prod(kept)
+    shape = (n_out, groups, *kept) if out_major else (groups, n_out, *kept)
+    y = torch.empty(shape, dtype=torch.complex64, device=xhat.device)
+    y_gs, y_os = (modes, groups * modes) if out_major else (n_out * modes, modes)
+    lib = _lib.get_lib()
+    xp, yp = torch.view_as_real(xhat).data_ptr(), torch.view_as_real(y).data_ptr()
+    with torch.cuda.device(xhat.device):
+        for t0, t1 in _specop_chunks(terms, n_out):
+            part = [(s, o - t0, c, t) for s, o, c, t in terms if t0 <= o < t1]
+            lib.spectral_op(xp, yp + 8 * t0 * y_os, kept=kept, groups=groups, n_src=n_src, n_out=t1 - t0, terms=part,
+                            tabs_a=[t.data_ptr() for t in tabs.a], tabs_b=[t.data_ptr() for t in tabs.b],
+                            n_tab=tabs.n_tab, y_group_stride=y_gs, y_out_stride=y_os, conj=conj, stream=_stream())
+    return y
+
+
+class SpectralOpFn(torch.autograd.Function):
+    """yhat[g, t] = sum_{j: out_j = t} coef_j 1/2 (prod_d a_d[tab_jd] + prod_d b_d[tab_jd]) xhat[g, src_j]
+    (sc_spectral_op): xhat (groups, n_src, *kept) complex64 -> (groups, n_out, *kept), or (n_out, groups, *kept) with
+    out_major.  The gradient is the same call with sources and outputs exchanged and the multipliers conjugated (so it
+    differentiates any number of times); the tables take none."""
+
+    @staticmethod
+    def forward(ctx, xhat, tabs, terms, n_out, conj=False, out_major=False):
+        ctx.tabs, ctx.terms, ctx.conj, ctx.out_major = tabs, tuple(terms), bool(conj), bool(out_major)
+        ctx.n_src = int(xhat.shape[1])
+        return _spectral_op(xhat, tabs, ctx.terms, int(n_out), ctx.conj, ctx.out_major)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.out_major:
+            g = g.transpose(0, 1)
+        back = tuple((o, s, c, t) for s, o, c, t in ctx.terms)
+        return SpectralOpFn.apply(g, ctx.tabs, back, ctx.n_src, not ctx.conj, False), None, None, None, None, None
+
+
 class EngineOps:
     """The three local stages of a (mode-parallel) spectral layer on the MI355X engine."""
 
@@ -898,6 +1019,11 @@ class EngineOps:
     @staticmethod
     def legendre_synthesis(c, tab):
         return LegendreSynthesisFn.apply(c, tab)
+
+    # the multiplier pass between the transforms of a spectral-derivative operator (differentiation.FourierDiff)
+    @staticmethod
+    def spectral_op(xhat, tabs, terms, n_out, conj=False, out_major=False):
+        return SpectralOpFn.apply(xhat, tabs, terms, n_out, conj, out_major)
 
     # one complex axis of a separable transform (the sharded dim of mpu.SpatialParallelSpectralConv):
     # x (B, L, n) complex -> (B, L, k) with kept row r reading FFT index rows[r], and its zero-padded inverse;
