@@ -307,6 +307,66 @@ typedef struct {
 } sc_specop_desc;
 int sc_spectral_op(const sc_specop_desc* desc, const float* xhat, float* yhat, void* stream);
 
+/* ---- banded real-space operators: finite differences and the Lp / H1 data losses ----
+ * neuralop/losses/differentiation.py's FiniteDiff (:11-660) is, along one axis, an N x N matrix with three interior
+ * bands and (non-periodic) two one-sided boundary rows of four entries; it, its transpose and D^T D are banded with
+ * half-width <= 3.  A table T[d] holds n_tab[d] such matrices of axis d as [n_tab[d]][dims[d]][7] fp32: entry o + 3 of
+ * row i multiplies the neighbour i + o (o = -3..3).
+ *   y[g, t, p] = scale[g] * scale_mul[0] * sum over terms j with term_out[j] = t of
+ *                term_coef[j] * sum_o T[axis_j][term_tab[j]][i_axis(p)][o + 3] * s[g, term_src[j], p + o stride_axis]
+ * u (groups, n_src, dims[0..ndim-1]) fp32 contiguous; s = u, or u - u2 where u2 (same shape) is given.  term_axis -1 is
+ * the identity, term_coef * s[p].  scale ([groups]) and scale_mul ([1]) are optional device pointers.  y element
+ * (g, t, p) lies at float offset g * y_group_stride + t * y_out_stride + p.  On a periodic axis neighbour indices wrap
+ * modulo dims[d] (any extent >= 1: the caller puts every matrix entry into exactly one tap); on a non-periodic axis
+ * (extent >= 4) a neighbour outside the line must have a zero table entry -- its address is clamped into the line, never
+ * read outside the buffer.  Every addressed y element is overwritten, an output without a term with zeros.  At most
+ * SC_BAND_MAX_TERMS terms plus term-less outputs, n_src <= 3, n_out <= 3.  Deterministic: no atomics. */
+#define SC_BAND_MAX_TERMS 12
+typedef struct {
+  int32_t ndim;                               /* 1..3                                                       */
+  int32_t n_src, n_out, n_terms;
+  int64_t dims[3];
+  int32_t periodic[3];
+  int32_t reserved;
+  int64_t groups;
+  int64_t y_group_stride, y_out_stride;       /* floats                                                     */
+  int32_t n_tab[3];
+  int32_t term_src[SC_BAND_MAX_TERMS], term_out[SC_BAND_MAX_TERMS];
+  int32_t term_axis[SC_BAND_MAX_TERMS], term_tab[SC_BAND_MAX_TERMS];
+  float term_coef[SC_BAND_MAX_TERMS];
+  const float* T[3];
+  const float* scale;
+  const float* scale_mul;
+} sc_band_desc;
+int sc_band_apply(const sc_band_desc* desc, const float* u, const float* u2, float* y, void* stream);
+
+/* The reductions of LpLoss / H1Loss (neuralop/losses/data_losses.py:21-491) over x, y (lines, dims..) fp32 contiguous,
+ * two launches.  Stage 1 writes per (line, chunk) the partial sums
+ *   h1 != 0:  num = sum_p [e^2 + sum_d (D_d e)^2],  den = sum_p [y^2 + sum_d (D_d y)^2],  e = x - y, D_d = T[d] ([dims[d]][7])
+ *   h1 == 0:  num = sum |e|^p,  den = sum |y|^p   (integer p >= 1; dims only give the point count)
+ * into ws ([lines][chunks][2] floats, sc_sobolev_workspace_bytes); a line is split over as many workgroups as fill the
+ * device (chunks != 0 in the descriptor asks for about that many).  Stage 2 (one workgroup) sums the chunks in a fixed
+ * order and writes per line v_l, dv[l] = factor * dv_l / dnum_l and loss[0] = factor * sum_l v_l, factor = 1 or 1 / lines:
+ *   relative == 0:  v = konst num, its p-th root with take_root (never for p = 1)
+ *   relative != 0:  v = num^(1/p) / (den^(1/p) + eps) with take_root (and p != 1), else num / (den + eps)
+ * H1 is p = 2.  sc_lp_grad: gx[l, i] = dv[l] * gout[0] * p |e_i|^(p-1) sign(e_i) (the H1 gradient is one sc_band_apply
+ * with the D^T D tables, sources x, y, scale = dv, scale_mul = gout).  Deterministic: no atomics. */
+typedef struct {
+  int32_t ndim;                               /* 1..3                                                       */
+  int32_t h1, p, relative, take_root, reduce_mean;
+  int32_t chunks;                             /* 0: chosen by the engine                                    */
+  int32_t periodic[3];
+  int64_t dims[3];
+  int64_t lines;
+  double konst, eps;
+  const float* T[3];                          /* h1: D of each axis                                         */
+} sc_sobolev_desc;
+size_t sc_sobolev_workspace_bytes(const sc_sobolev_desc* desc);
+int sc_sobolev_sums(const sc_sobolev_desc* desc, const float* x, const float* y, float* ws, size_t ws_bytes, float* v,
+                    float* dv, float* loss, void* stream);
+int sc_lp_grad(const sc_sobolev_desc* desc, const float* x, const float* y, const float* dv, const float* gout,
+               float* gx, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -10,7 +10,8 @@ from .optim import AdamW  # noqa: F401
 from .galore import TensorGaLoreProjector  # noqa: F401
 from .spherical import SHT, SphericalConv  # noqa: F401
 from .harmonics import InverseRealSHT, RealSHT, install_torch_harmonics  # noqa: F401
-from .differentiation import FourierDiff  # noqa: F401
+from .differentiation import FiniteDiff, FourierDiff  # noqa: F401
+from .losses import H1Loss, LpLoss  # noqa: F401
 from .graph import GraphedStep, capture_step  # noqa: F401
 
 __version__ = "0.1.0"

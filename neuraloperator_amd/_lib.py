@@ -125,6 +125,25 @@ class SpecopDesc(Structure):                                # sc_specop_desc
                 ("A", c_void_p * 3), ("B", c_void_p * 3)]
 
 
+SC_BAND_MAX_TERMS = 12
+
+
+class BandDesc(Structure):                                  # sc_band_desc
+    _fields_ = [("ndim", c_int32), ("n_src", c_int32), ("n_out", c_int32), ("n_terms", c_int32),
+                ("dims", c_int64 * 3), ("periodic", c_int32 * 3), ("reserved", c_int32), ("groups", c_int64),
+                ("y_group_stride", c_int64), ("y_out_stride", c_int64), ("n_tab", c_int32 * 3),
+                ("term_src", c_int32 * SC_BAND_MAX_TERMS), ("term_out", c_int32 * SC_BAND_MAX_TERMS),
+                ("term_axis", c_int32 * SC_BAND_MAX_TERMS), ("term_tab", c_int32 * SC_BAND_MAX_TERMS),
+                ("term_coef", ctypes.c_float * SC_BAND_MAX_TERMS), ("T", c_void_p * 3), ("scale", c_void_p),
+                ("scale_mul", c_void_p)]
+
+
+class SobolevDesc(Structure):                               # sc_sobolev_desc
+    _fields_ = [("ndim", c_int32), ("h1", c_int32), ("p", c_int32), ("relative", c_int32), ("take_root", c_int32),
+                ("reduce_mean", c_int32), ("chunks", c_int32), ("periodic", c_int32 * 3), ("dims", c_int64 * 3),
+                ("lines", c_int64), ("konst", ctypes.c_double), ("eps", ctypes.c_double), ("T", c_void_p * 3)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -183,7 +202,8 @@ class ScEngineLib:
                "sc_peer_window_close", "sc_peer_window_free", "sc_peer_all_to_all", "sc_peer_window_control", "sc_pointwise_linear_forward_ex",
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
                "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
-               "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op"]
+               "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op",
+               "sc_band_apply", "sc_sobolev_workspace_bytes", "sc_sobolev_sums", "sc_lp_grad"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -334,6 +354,15 @@ class ScEngineLib:
             getattr(L, s).restype = c_int
         L.sc_spectral_op.argtypes = [POINTER(SpecopDesc), c_void_p, c_void_p, c_void_p]
         L.sc_spectral_op.restype = c_int
+        L.sc_band_apply.argtypes = [POINTER(BandDesc), c_void_p, c_void_p, c_void_p, c_void_p]
+        L.sc_band_apply.restype = c_int
+        L.sc_sobolev_workspace_bytes.argtypes = [POINTER(SobolevDesc)]
+        L.sc_sobolev_workspace_bytes.restype = c_size_t
+        L.sc_sobolev_sums.argtypes = [POINTER(SobolevDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]
+        L.sc_sobolev_sums.restype = c_int
+        L.sc_lp_grad.argtypes = [POINTER(SobolevDesc)] + [c_void_p] * 6
+        L.sc_lp_grad.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -642,6 +671,53 @@ class ScEngineLib:
             for i in range(nd):
                 d.term_tab[j][i] = tab[i]
         self._check(self.lib.sc_spectral_op(byref(d), x_ptr, y_ptr, stream))
+
+    def band_apply(self, u_ptr, u2_ptr, y_ptr, *, dims, periodic, groups, n_src, n_out, terms, tabs, n_tab,
+                   y_group_stride, y_out_stride, scale=0, scale_mul=0, stream=0):
+        """y[g, t] = scale[g] scale_mul sum over terms (src, out, coef, axis, tab) with out = t of coef * (banded
+        matrix tab of the axis, or the identity for axis -1) applied to u[g, src] (- u2[g, src]) (sc_band_apply); tabs
+        the device pointers of the per-axis tables [n_tab_d][dims_d][7] fp32"""
+        d = BandDesc()
+        nd = len(dims)
+        if len(terms) > SC_BAND_MAX_TERMS or not 1 <= nd <= 3:
+            raise EngineError(f"sc_band_apply: {len(terms)} terms over {nd} dims (at most {SC_BAND_MAX_TERMS} terms of "
+                              "1 to 3 dims per call)")
+        d.ndim, d.n_src, d.n_out, d.n_terms = nd, n_src, n_out, len(terms)
+        d.groups, d.y_group_stride, d.y_out_stride = groups, y_group_stride, y_out_stride
+        d.scale, d.scale_mul = scale or None, scale_mul or None
+        for i in range(nd):
+            d.dims[i], d.periodic[i], d.n_tab[i], d.T[i] = dims[i], int(bool(periodic[i])), n_tab[i], tabs[i] or None
+        for j, (src, out, coef, axis, tab) in enumerate(terms):
+            d.term_src[j], d.term_out[j], d.term_coef[j], d.term_axis[j], d.term_tab[j] = src, out, coef, axis, tab
+        self._check(self.lib.sc_band_apply(byref(d), u_ptr or None, u2_ptr or None, y_ptr or None, stream))
+
+    @staticmethod
+    def sobolev_desc(*, dims, periodic=None, lines, h1, p=2, relative=True, take_root=True, reduce_mean=False,
+                     konst=1.0, eps=0.0, tabs=None, chunks=0):
+        d = SobolevDesc()
+        d.ndim, d.h1, d.p, d.relative, d.take_root = len(dims), int(bool(h1)), int(p), int(bool(relative)), int(bool(take_root))
+        d.reduce_mean, d.chunks, d.lines, d.konst, d.eps = int(bool(reduce_mean)), int(chunks), int(lines), konst, eps
+        if not 1 <= len(dims) <= 3:
+            raise EngineError(f"sc_sobolev_sums: {len(dims)} dims (1 to 3)")
+        for i in range(len(dims)):
+            d.dims[i] = dims[i]
+            d.periodic[i] = 1 if periodic is None else int(bool(periodic[i]))
+            d.T[i] = (tabs[i] or None) if tabs is not None else None
+        return d
+
+    def sobolev_workspace_bytes(self, desc):
+        return int(self.lib.sc_sobolev_workspace_bytes(byref(desc)))
+
+    def sobolev_sums(self, desc, x_ptr, y_ptr, ws_ptr, ws_bytes, v_ptr, dv_ptr, loss_ptr, stream=0):
+        """the per-line norms v, their derivatives dv by the numerator sums (times the reduction factor) and the
+        reduced loss of LpLoss / H1Loss: two launches (sc_sobolev_sums)"""
+        self._check(self.lib.sc_sobolev_sums(byref(desc), x_ptr or None, y_ptr or None, ws_ptr or None, ws_bytes,
+                                             v_ptr or None, dv_ptr or None, loss_ptr or None, stream))
+
+    def lp_grad(self, desc, x_ptr, y_ptr, dv_ptr, gout_ptr, gx_ptr, stream=0):
+        """gx[l, i] = dv[l] gout p |x - y|^(p-1) sign(x - y) (sc_lp_grad)"""
+        self._check(self.lib.sc_lp_grad(byref(desc), x_ptr or None, y_ptr or None, dv_ptr or None, gout_ptr or None,
+                                        gx_ptr or None, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

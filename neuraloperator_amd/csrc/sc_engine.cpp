@@ -45,6 +45,7 @@
 #include "sc_kernels_bicubic.h"
 #include "sc_kernels_sht.h"
 #include "sc_kernels_specop.h"
+#include "sc_kernels_stencil.h"
 #include "sc_kernels_wire.h"
 
 // ------------------------------------------------------------------------------------------
@@ -3611,6 +3612,170 @@ extern "C" int sc_spectral_op(const sc_specop_desc* d, const float* xhat, float*
   const dim3 grid((unsigned)rows, (unsigned)tiles, (unsigned)((d->groups + gpw - 1) / gpw));
   SC_LAUNCH(k_spectral_op, grid, dim3(256), 0, (sc_stream_t)stream, xhat, yhat, a);
   return sc_check_launch("k_spectral_op");
+}
+
+// ---- banded real-space operators: finite differences, Lp / H1 losses (sc_kernels_stencil.h) ------------------------
+// the field as (d0, d1, d2), missing leading axes of extent 1 (periodic, never referenced by a term)
+static bool band_geom(const int ndim, const int64_t* dims, const int32_t* periodic, BandGeom* g, const char** why) {
+  int64_t d[3] = {1, 1, 1};
+  int per[3] = {1, 1, 1};
+  for (int i = 0; i < ndim; ++i) {
+    if (dims[i] < 1 || dims[i] >= ((int64_t)1 << 24)) { *why = "axis extent out of range"; return false; }
+    if (!periodic[i] && dims[i] < 4) { *why = "a non-periodic axis needs at least 4 points"; return false; }
+    d[3 - ndim + i] = dims[i];
+    per[3 - ndim + i] = periodic[i] ? 1 : 0;
+  }
+  if (d[0] * d[1] * d[2] >= ((int64_t)1 << 31)) { *why = "field above 2^31 points"; return false; }
+  g->d0 = (int)d[0]; g->d1 = (int)d[1]; g->d2 = (int)d[2];
+  g->per0 = per[0]; g->per1 = per[1]; g->per2 = per[2];
+  g->tiles_r = (g->d1 + BAND_TR - 1) / BAND_TR;
+  g->tiles_c = (g->d2 + BAND_TC - 1) / BAND_TC;
+  return true;
+}
+
+extern "C" int sc_band_apply(const sc_band_desc* d, const float* u, const float* u2, float* y, void* stream) {
+  SC_CHECK_ARG(d, "null argument");
+  SC_CHECK_ARG(d->ndim >= 1 && d->ndim <= 3, "band_apply: ndim must be 1, 2 or 3");
+  SC_CHECK_ARG(d->n_src >= 1 && d->n_src <= BAND_MAX_SRC, "band_apply: 1 to 3 sources");
+  SC_CHECK_ARG(d->n_out >= 1 && d->n_out <= 3, "band_apply: 1 to 3 outputs");
+  SC_CHECK_ARG(d->n_terms >= 0 && d->n_terms <= SC_BAND_MAX_TERMS, "band_apply: more than SC_BAND_MAX_TERMS terms");
+  SC_CHECK_ARG(d->groups >= 0 && d->groups < ((int64_t)1 << 40), "band_apply: group count out of range");
+  SC_CHECK_ARG(d->y_group_stride >= 0 && d->y_out_stride >= 0, "band_apply: negative output stride");
+  BandArgs a;
+  std::memset(&a, 0, sizeof(a));
+  const char* why = "";
+  if (!band_geom(d->ndim, d->dims, d->periodic, &a.g, &why)) return sc_fail(std::string("sc_engine: band_apply: ") + why);
+  const int shift = 3 - d->ndim;
+  for (int j = 0; j < d->n_terms; ++j) {
+    SC_CHECK_ARG(d->term_src[j] >= 0 && d->term_src[j] < d->n_src, "band_apply: term source out of range");
+    SC_CHECK_ARG(d->term_out[j] >= 0 && d->term_out[j] < d->n_out, "band_apply: term output out of range");
+    const int ax = d->term_axis[j];
+    SC_CHECK_ARG(ax >= -1 && ax < d->ndim, "band_apply: term axis out of range");
+    if (ax >= 0) {
+      SC_CHECK_ARG(d->n_tab[ax] >= 1 && d->n_tab[ax] <= 255, "band_apply: 1 to 255 tables per axis");
+      SC_CHECK_ARG(d->term_tab[j] >= 0 && d->term_tab[j] < d->n_tab[ax], "band_apply: table out of range");
+      SC_CHECK_ARG(d->T[ax], "band_apply: null table");
+    }
+  }
+  // slots: the terms grouped by output in their given order, plus one zero slot per output without a term
+  int n = 0;
+  for (int t = 0; t < d->n_out; ++t) {
+    const int first = n;
+    int src[BAND_SLOTS], axis[BAND_SLOTS], tab[BAND_SLOTS];
+    for (int j = 0; j <= d->n_terms; ++j) {
+      const bool zero = j == d->n_terms;
+      if (zero ? n != first : d->term_out[j] != t) continue;
+      SC_CHECK_ARG(n < BAND_SLOTS, "band_apply: terms plus outputs without a term exceed SC_BAND_MAX_TERMS");
+      a.coef[n] = zero ? 0.f : d->term_coef[j];
+      src[n] = zero ? 0 : d->term_src[j];
+      axis[n] = zero ? BAND_AX_ZERO : d->term_axis[j] < 0 ? BAND_AX_IDENT : d->term_axis[j] + shift;
+      tab[n] = zero || d->term_axis[j] < 0 ? 0 : d->term_tab[j];
+      ++n;
+    }
+    for (int k = first; k < n; ++k)
+      a.info[k] = band_info((k == first ? BAND_FIRST : 0) | (k == n - 1 ? BAND_LAST : 0), src[k], t, axis[k], tab[k]);
+  }
+  if (d->groups == 0) return 0;
+  SC_CHECK_ARG(u && y, "null argument");
+  for (int i = 0; i < d->ndim; ++i) a.tab[shift + i] = d->T[i];
+  a.scale = d->scale;
+  a.scale_mul = d->scale_mul;
+  a.y_gs = d->y_group_stride;
+  a.y_os = d->y_out_stride;
+  a.n_src = d->n_src;
+  a.n_slots = n;
+  const int64_t blocks = d->groups * a.g.d0 * a.g.tiles_r * a.g.tiles_c;
+  SC_CHECK_ARG(blocks < ((int64_t)1 << 31) - 1, "band_apply: too many tiles for one launch");
+  SC_LAUNCH(k_band_apply, dim3((unsigned)blocks), dim3(256), 0, (sc_stream_t)stream, u, u2, y, a);
+  return sc_check_launch("k_band_apply");
+}
+
+// the split of a line over workgroups; false (with a reason) for a refused descriptor
+static bool sob_plan(const sc_sobolev_desc* d, SobArgs* a, const char** why) {
+  std::memset(a, 0, sizeof(*a));
+  if (!d) { *why = "null argument"; return false; }
+  if (d->ndim < 1 || d->ndim > 3) { *why = "ndim must be 1, 2 or 3"; return false; }
+  if (d->p < 1 || d->p > 64) { *why = "p must be an integer from 1 to 64"; return false; }
+  if (d->h1 && d->p != 2) { *why = "the H1 norm is p = 2"; return false; }
+  if (d->lines < 0 || d->lines >= ((int64_t)1 << 31) - 1) { *why = "line count out of range"; return false; }
+  if (d->chunks < 0 || d->chunks > (1 << 20)) { *why = "chunk count out of range"; return false; }
+  int32_t all_periodic[3] = {1, 1, 1};
+  if (!band_geom(d->ndim, d->dims, d->h1 ? d->periodic : all_periodic, &a->g, why)) return false;
+  a->npts = (int64_t)a->g.d0 * a->g.d1 * a->g.d2;
+  a->h1 = d->h1 ? 1 : 0;
+  a->p = d->p;
+  const int64_t lines = d->lines > 0 ? d->lines : 1;
+  // units of work per line: tiles (H1) or runs of SOB_LP_UNIT points (Lp)
+  const int64_t units = a->h1 ? (int64_t)a->g.d0 * a->g.tiles_r * a->g.tiles_c : (a->npts + SOB_LP_UNIT - 1) / SOB_LP_UNIT;
+  int64_t want = d->chunks ? d->chunks : (4 * (int64_t)sc_cu_count() + lines - 1) / lines;
+  if (want > units) want = units;
+  if (want < 1) want = 1;
+  const int64_t per = (units + want - 1) / want;
+  a->chunks = (int)((units + per - 1) / per);
+  a->units = units;
+  a->per_chunk = a->h1 ? per : per * SOB_LP_UNIT;
+  if (lines * a->chunks >= ((int64_t)1 << 31) - 1) { *why = "too many workgroups for one launch"; return false; }
+  return true;
+}
+
+extern "C" size_t sc_sobolev_workspace_bytes(const sc_sobolev_desc* d) {
+  SobArgs a;
+  const char* why = "";
+  if (!sob_plan(d, &a, &why)) return 0;
+  return (size_t)d->lines * a.chunks * 2 * sizeof(float);
+}
+
+extern "C" int sc_sobolev_sums(const sc_sobolev_desc* d, const float* x, const float* y, float* ws, size_t ws_bytes,
+                               float* v, float* dv, float* loss, void* stream) {
+  SobArgs a;
+  const char* why = "";
+  if (!sob_plan(d, &a, &why)) return sc_fail(std::string("sc_engine: sobolev_sums: ") + why);
+  SC_CHECK_ARG(loss, "null argument");
+  SC_CHECK_ARG(d->lines == 0 || (x && y && ws && v && dv), "null argument");
+  SC_CHECK_ARG(ws_bytes >= (size_t)d->lines * a.chunks * 2 * sizeof(float), "sobolev_sums: workspace too small");
+  if (a.h1)
+    for (int i = 0; i < d->ndim; ++i) {
+      SC_CHECK_ARG(d->T[i], "sobolev_sums: null table");
+      a.tab[3 - d->ndim + i] = d->T[i];
+    }
+  a.vec = a.npts % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  FinishArgs f;
+  std::memset(&f, 0, sizeof(f));
+  f.lines = d->lines;
+  f.chunks = a.chunks;
+  f.sub = 1;
+  while (f.sub < 256 && f.sub < a.chunks) f.sub <<= 1;
+  f.p = d->p;
+  f.relative = d->relative ? 1 : 0;
+  f.root = d->take_root && d->p != 1 ? 1 : 0;
+  f.konst = (float)d->konst;
+  f.eps = (float)d->eps;
+  f.factor = d->reduce_mean && d->lines > 0 ? (float)(1.0 / (double)d->lines) : 1.f;
+  if (d->lines > 0) {
+    SC_LAUNCH(k_sobolev_partial, dim3((unsigned)(d->lines * a.chunks)), dim3(256), 0, (sc_stream_t)stream, x, y, ws, a);
+    if (int e = sc_check_launch("k_sobolev_partial")) return e;
+  }
+  SC_LAUNCH(k_loss_finish, dim3(1), dim3(256), 0, (sc_stream_t)stream, (const float*)ws, v, dv, loss, f);
+  return sc_check_launch("k_loss_finish");
+}
+
+extern "C" int sc_lp_grad(const sc_sobolev_desc* d, const float* x, const float* y, const float* dv, const float* gout,
+                          float* gx, void* stream) {
+  SobArgs s;
+  const char* why = "";
+  if (!sob_plan(d, &s, &why)) return sc_fail(std::string("sc_engine: lp_grad: ") + why);
+  SC_CHECK_ARG(!d->h1, "lp_grad: the H1 gradient is a band_apply call");
+  if (d->lines == 0) return 0;
+  SC_CHECK_ARG(x && y && dv && gout && gx, "null argument");
+  LpGradArgs a;
+  a.npts = s.npts;
+  a.units = (s.npts + SOB_LP_UNIT - 1) / SOB_LP_UNIT;
+  a.p = d->p;
+  a.vec = s.npts % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) |
+                                reinterpret_cast<uintptr_t>(gx)) & 15) == 0;
+  SC_CHECK_ARG(d->lines * a.units < ((int64_t)1 << 31) - 1, "lp_grad: too many workgroups for one launch");
+  SC_LAUNCH(k_lp_grad, dim3((unsigned)(d->lines * a.units)), dim3(256), 0, (sc_stream_t)stream, x, y, dv, gout, gx, a);
+  return sc_check_launch("k_lp_grad");
 }
 
 extern "C" int sc_modegemm_path(const sc_modegemm_desc* d) {

@@ -27,7 +27,15 @@ Reproduced as the reference has them:
   * 1-d runs on ``rfft`` / ``irfft`` with the mask on the half spectrum (:1186-1204).
 
 Non-fp32 real input is computed in fp32 and returned as fp32 (as ``RealSHT`` does).  Fourier continuation
-(``use_fc``) is not provided."""
+(``use_fc``) is not provided.
+
+``FiniteDiff`` (the reference's :11-660) is the other half of the file: along one axis every one of its operators is an
+N x N matrix with three interior bands and, on a non-periodic axis, two one-sided boundary rows of four entries.  The
+engine holds D, D^T (orders 1 and 2) of every axis as 7-band tables built in float64 (engine.finite_diff_tables) and
+every method is ONE ``sc_band_apply`` launch; ``laplacian`` / ``divergence`` / ``curl`` sum inside the kernel.  The
+backward pass is the same launch with the transposed tables and the term list transposed, so it differentiates any
+number of times.  One difference: a non-periodic axis shorter than 4 points raises ``ValueError`` (the reference's
+boundary stencils die there with an ``IndexError``).  ``central_diff_*`` and ``non_uniform_fd`` are not provided."""
 import math
 
 import numpy as np
@@ -242,5 +250,110 @@ class FourierDiff:
         terms = [(2, 0, 1.0, (0, 1, 0)), (1, 0, -1.0, (0, 0, 1)),        # dw/dy - dv/dz
                  (0, 1, 1.0, (0, 0, 1)), (2, 1, -1.0, (1, 0, 0)),        # du/dz - dw/dx
                  (1, 2, 1.0, (1, 0, 0)), (0, 2, -1.0, (0, 1, 0))]        # dv/dx - du/dy
+        y, lead, spatial = self._apply(u, 3, terms, 3, False)
+        return y.reshape(*lead, 3, *spatial)
+
+
+class FiniteDiff:
+    """Finite differences on a regular grid: the reference's class on the engine.
+
+    Parameters as ``neuralop.losses.differentiation.FiniteDiff``: ``dim`` 1, 2 or 3 (the spatial dims are the last
+    ``dim`` of the input, any leading dims); ``h`` the grid spacing, one number or one per axis; ``periodic_in_x/y/z``
+    central differences through the wrap (True) or one-sided third-order stencils at the two ends (False)."""
+
+    def __init__(self, dim, h=1.0, periodic_in_x=True, periodic_in_y=True, periodic_in_z=True):
+        if dim not in [1, 2, 3]:
+            raise ValueError("dim must be 1, 2, or 3")
+        self.dim = dim
+        if isinstance(h, (int, float)):
+            self.h = tuple(h for _ in range(dim))
+        else:
+            if len(h) != dim:
+                raise ValueError(f"For {dim}D, h must be a float or a tuple of length {dim}")
+            self.h = tuple(h)
+        self.periodic_in_x = periodic_in_x
+        if dim >= 2:
+            self.periodic_in_y = periodic_in_y
+        if dim >= 3:
+            self.periodic_in_z = periodic_in_z
+
+    # ------------------------------------------------------------------------------------------ the one code path
+    def _periodic(self):
+        return tuple(bool(getattr(self, "periodic_in_" + _AXES[d])) for d in range(self.dim))
+
+    def _apply(self, u, n_src, terms, n_out, out_major):
+        """u (..., [n_src,] *spatial); terms (src, out, coef, axis, order) -> (n_out, groups, *spatial) if out_major
+        else (groups, n_out, *spatial), and the leading shape"""
+        if u.is_complex():
+            raise TypeError("FiniteDiff differentiates real fields")
+        for t in terms:
+            if t[4] not in (1, 2):
+                raise ValueError("Only 1st and 2nd order derivatives currently supported")
+        if u.dim() < self.dim + (1 if n_src else 0):
+            raise ValueError(f"FiniteDiff: a {u.dim()}-d tensor has no {self.dim} spatial dims")
+        spatial = tuple(int(s) for s in u.shape[-self.dim:])
+        lead = tuple(u.shape[:u.dim() - self.dim - (1 if n_src else 0)])
+        periodic = self._periodic()
+        for n, per in zip(spatial, periodic):
+            if not per and n < 4:
+                raise ValueError(f"FiniteDiff: a non-periodic axis needs at least 4 points for its one-sided boundary "
+                                 f"stencils, got {n}")
+        engine._require_gpu(u, "field")
+        tabs = engine.finite_diff_tables(u.device, spatial, self.h, periodic)
+        rows = tuple((s, o, float(c), a, od - 1) for s, o, c, a, od in terms)          # table rows: D1, D2, D1^T, D2^T
+        x = u.float().reshape(-1, n_src or 1, *spatial)
+        return engine.EngineOps.band_apply(x, tabs, rows, n_out, out_major), lead, spatial
+
+    def _d(self, u, axis, order):
+        y, _, _ = self._apply(u, 0, [(0, 0, 1.0, axis, order)], 1, True)
+        return y.reshape(u.shape)
+
+    # ------------------------------------------------------------------------------------------ public methods
+    def dx(self, u, order=1):
+        return self._d(u, 0, order)
+
+    def dy(self, u, order=1):
+        if self.dim < 2:
+            raise ValueError("dy is only available for 2D and 3D")
+        return self._d(u, 1, order)
+
+    def dz(self, u, order=1):
+        if self.dim < 3:
+            raise ValueError("dz is only available for 3D")
+        return self._d(u, 2, order)
+
+    def laplacian(self, u):
+        """sum of the second derivatives, one output summed inside the kernel"""
+        y, _, _ = self._apply(u, 0, [(0, 0, 1.0, d, 2) for d in range(self.dim)], 1, True)
+        return y.reshape(u.shape)
+
+    def gradient(self, u):
+        """(..., *spatial) -> (..., dim, *spatial); 1-d: du/dx shaped like u, as the reference returns it"""
+        if self.dim == 1:
+            return self._d(u, 0, 1)
+        y, lead, spatial = self._apply(u, 0, [(0, d, 1.0, d, 1) for d in range(self.dim)], self.dim, False)
+        return y.reshape(*lead, self.dim, *spatial)
+
+    def divergence(self, u):
+        """(..., dim, *spatial) -> (..., *spatial)"""
+        if u.shape[-self.dim - 1] != self.dim:
+            raise ValueError(f"Input must be a {self.dim}D vector field with {self.dim} components")
+        y, lead, spatial = self._apply(u, self.dim, [(d, 0, 1.0, d, 1) for d in range(self.dim)], 1, False)
+        return y.reshape(*lead, *spatial)
+
+    def curl(self, u):
+        """2-d: (..., 2, nx, ny) -> (..., nx, ny), dv/dx - du/dy; 3-d: (..., 3, *spatial) -> the same shape"""
+        if self.dim == 1:
+            raise ValueError("Curl is not defined for 1D")
+        elif self.dim == 2:
+            if u.shape[-3] != 2:
+                raise ValueError("Input must be a 2D vector field with 2 components")
+            y, lead, spatial = self._apply(u, 2, [(1, 0, 1.0, 0, 1), (0, 0, -1.0, 1, 1)], 1, False)
+            return y.reshape(*lead, *spatial)
+        if u.shape[-4] != 3:
+            raise ValueError("Input must be a 3D vector field with 3 components")
+        terms = [(2, 0, 1.0, 1, 1), (1, 0, -1.0, 2, 1),        # dw/dy - dv/dz
+                 (0, 1, 1.0, 2, 1), (2, 1, -1.0, 0, 1),        # du/dz - dw/dx
+                 (1, 2, 1.0, 0, 1), (0, 2, -1.0, 1, 1)]        # dv/dx - du/dy
         y, lead, spatial = self._apply(u, 3, terms, 3, False)
         return y.reshape(*lead, 3, *spatial)

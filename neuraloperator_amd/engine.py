@@ -986,6 +986,241 @@ class SpectralOpFn(torch.autograd.Function):
         return SpectralOpFn.apply(g, ctx.tabs, back, ctx.n_src, not ctx.conj, False), None, None, None, None, None
 
 
+# ---- banded real-space operators: finite differences and the Lp / H1 losses (sc_band_apply, sc_sobolev_sums) -------
+BAND_HALF = 3                                  # half-width of every table: taps -3 .. 3
+
+
+def band_table(m, periodic):
+    """Cut a dense (N, N) float64 matrix to its 7 bands: t[i, o + 3] multiplies the neighbour i + o, wrapped modulo N
+    on a periodic axis (each matrix entry goes into exactly ONE tap, the nearest, so extents 1, 2, 3 -- where the
+    offsets alias -- come out right).  Asserts that nothing outside the band is non-zero."""
+    import numpy as np
+    n = m.shape[0]
+    rows = np.arange(n)
+    t = np.zeros((n, 2 * BAND_HALF + 1), dtype=np.float64)
+    claimed = np.zeros((n, n), dtype=bool)
+    for o in sorted(range(-BAND_HALF, BAND_HALF + 1), key=abs):
+        cols = rows + o
+        inside = np.ones(n, dtype=bool) if periodic else (cols >= 0) & (cols < n)
+        cols = cols % n
+        take = inside & ~claimed[rows, cols]
+        t[take, o + BAND_HALF] = m[rows[take], cols[take]]
+        claimed[rows[take], cols[take]] = True
+    assert not np.any(m[~claimed]), "finite-difference matrix has an entry outside its 7 bands"
+    return t
+
+
+def fd_matrix(n, h, order, periodic):
+    """The dense float64 (N, N) matrix of FiniteDiff's derivative of `order` 1 or 2 along one axis
+    (neuralop/losses/differentiation.py:328-373): central differences inside (through the wrap on a periodic axis),
+    third-order one-sided rows of four entries at the two ends otherwise."""
+    import numpy as np
+    if order not in (1, 2):
+        raise ValueError("Only 1st and 2nd order derivatives currently supported")
+    if not periodic and n < 4:
+        raise ValueError(f"FiniteDiff: a non-periodic axis needs at least 4 points for its one-sided boundary "
+                         f"stencils, got {n}")
+    m = np.zeros((n, n), dtype=np.float64)
+    rows = np.arange(n)
+    inner, lo, hi = ((-1.0, 0.0, 1.0), (-11.0, 18.0, -9.0, 2.0), (-2.0, 9.0, -18.0, 11.0)) if order == 1 else \
+        ((1.0, -2.0, 1.0), (2.0, -5.0, 4.0, -1.0), (-1.0, 4.0, -5.0, 2.0))
+    den = 2.0 * h if order == 1 else h ** 2
+    end = 6.0 * h if order == 1 else h ** 2
+    sel = rows if periodic else rows[1:-1]
+    for o, c in zip((-1, 0, 1), inner):
+        np.add.at(m, (sel, (sel + o) % n), c / den)
+    if not periodic:
+        m[0, :4] = np.array(lo) / end
+        m[-1, -4:] = np.array(hi) / end
+    return m
+
+
+class BandTables:
+    """Per-axis banded tables of sc_band_apply on one device: t[d] fp32 (n_tab_d, dims_d, 7); adj[d][r] is the row of
+    axis d that holds the TRANSPOSE of row r (the backward pass of a term).  Built once in float64 and rounded once;
+    constants of the operator, they take no gradient."""
+
+    def __init__(self, t, periodic, adj):
+        if not 1 <= len(t) <= 3 or len(periodic) != len(t) or len(adj) != len(t):
+            raise ValueError("band tables: one table per axis, 1 to 3 axes")
+        for ta, ad in zip(t, adj):
+            if ta.dtype != torch.float32 or ta.dim() != 3 or ta.shape[2] != 2 * BAND_HALF + 1 or not ta.is_contiguous() \
+                    or ta.device != t[0].device or len(ad) != ta.shape[0]:
+                raise ValueError("band tables: contiguous fp32 (n_tab, extent, 7) on one device")
+        self.t, self.periodic, self.adj = list(t), tuple(bool(p) for p in periodic), [tuple(a) for a in adj]
+        self.dims = tuple(int(x.shape[1]) for x in t)
+        self.n_tab = tuple(int(x.shape[0]) for x in t)
+        self.device = t[0].device
+
+
+_BAND_TABLES = collections.OrderedDict()       # (device, key) -> BandTables, least recently used first
+
+
+def get_band_tables(device, key, build):
+    """Cached device tables; ``key`` = (kind, dims, h, periodic flags, orders), ``build()`` returns on a miss the host
+    tables (one float64 array (n_tab, extent, 7) per axis) and the transpose map ``adj``."""
+    dev = torch.device(device)
+    full = (dev.type, dev.index if dev.index is not None or dev.type != "cuda" else torch.cuda.current_device(), key)
+    with _PLAN_LOCK:
+        tabs = _BAND_TABLES.get(full)
+        if tabs is not None:
+            _BAND_TABLES.move_to_end(full)
+            return tabs
+    host, periodic, adj = build()
+    tabs = BandTables([torch.from_numpy(t).to(torch.float32).contiguous().to(dev) for t in host], periodic, adj)
+    with _PLAN_LOCK:
+        _BAND_TABLES[full] = tabs
+        while len(_BAND_TABLES) > MAX_CACHED_SPEC_TABLES:
+            _BAND_TABLES.popitem(last=False)
+    return tabs
+
+
+def finite_diff_tables(device, dims, h, periodic, kind="fd"):
+    """kind "fd": rows D1, D2, D1^T, D2^T of every axis (FiniteDiff and its backward); kind "h1": rows D1, D1^T D1 (the
+    sums and the gradient of H1Loss).  From the dense float64 matrix of each axis, cut to 7 bands."""
+    dims, h, periodic = tuple(int(n) for n in dims), tuple(float(v) for v in h), tuple(bool(p) for p in periodic)
+
+    def build():
+        host, adj = [], []
+        for n, hd, per in zip(dims, h, periodic):
+            d1 = fd_matrix(n, hd, 1, per)
+            if kind == "fd":
+                d2 = fd_matrix(n, hd, 2, per)
+                mats, a = [d1, d2, d1.T, d2.T], (2, 3, 0, 1)
+            else:
+                mats, a = [d1, d1.T @ d1], (None, 1)
+            import numpy as np
+            host.append(np.stack([band_table(m, per) for m in mats]))
+            adj.append(a)
+        return host, periodic, adj
+
+    return get_band_tables(device, (kind, dims, h, periodic, (1, 2)), build)
+
+
+def _band_apply(u, u2, tabs, terms, n_out, out_major, scale=None, scale_mul=None):
+    """u (groups, n_src, *dims) fp32 -> (n_out, groups, *dims) if out_major else (groups, n_out, *dims); terms: tuples
+    (src, out, coef, axis, table row), axis -1 = identity.  One launch."""
+    _require_gpu(u, "field")
+    _require_gpu(tabs.t[0], "band tables")
+    for other, what in ((u2, "second source"), (scale, "scale"), (scale_mul, "scale")):
+        if other is not None:
+            _require_gpu(other, what)
+            if other.device != u.device or other.dtype != torch.float32 or not other.is_contiguous():
+                raise ValueError(f"band apply: {what} must be contiguous fp32 on {u.device}")
+    if tabs.device != u.device:
+        raise ValueError(f"band tables on {tabs.device}, field on {u.device}")
+    if u.dtype != torch.float32:
+        raise ValueError("band apply: fp32 fields")
+    u = u.contiguous()
+    groups, n_src = int(u.shape[0]), int(u.shape[1])
+    dims = tuple(int(k) for k in u.shape[2:])
+    if dims != tabs.dims:
+        raise ValueError(f"field {dims} against tables for {tabs.dims}")
+    if u2 is not None and u2.shape != u.shape:
+        raise ValueError(f"band apply: second source {tuple(u2.shape)} against {tuple(u.shape)}")
+    if scale is not None and scale.numel() != groups or scale_mul is not None and scale_mul.numel() != 1:
+        raise ValueError("band apply: scale holds one value per group, scale_mul one value")
+    for src, out, _, axis, tab in terms:
+        if not (0 <= src < n_src and 0 <= out < n_out and -1 <= axis < len(dims)
+                and (axis < 0 or 0 <= tab < tabs.n_tab[axis])):
+            raise ValueError(f"band apply: term {(src, out, axis, tab)} outside {n_src} sources, {n_out} outputs, "
+                             f"{tabs.n_tab} tables")
+    pts = math.prod(dims)
+    y = torch.empty((n_out, groups, *dims) if out_major else (groups, n_out, *dims), dtype=torch.float32, device=u.device)
+    y_gs, y_os = (pts, groups * pts) if out_major else (n_out * pts, pts)
+    with torch.cuda.device(u.device):
+        _lib.get_lib().band_apply(u.data_ptr(), 0 if u2 is None else u2.data_ptr(), y.data_ptr(), dims=dims,
+                                  periodic=tabs.periodic, groups=groups, n_src=n_src, n_out=n_out, terms=terms,
+                                  tabs=[t.data_ptr() for t in tabs.t], n_tab=tabs.n_tab, y_group_stride=y_gs,
+                                  y_out_stride=y_os, scale=0 if scale is None else scale.data_ptr(),
+                                  scale_mul=0 if scale_mul is None else scale_mul.data_ptr(), stream=_stream())
+    return y
+
+
+class BandApplyFn(torch.autograd.Function):
+    """y[g, t] = sum_{j: out_j = t} coef_j M_j u[g, src_j], M_j a banded matrix along one axis or the identity
+    (sc_band_apply): u (groups, n_src, *dims) fp32 -> (groups, n_out, *dims), or (n_out, groups, *dims) with out_major.
+    The gradient is the same launch with sources and outputs exchanged and the transposed tables, so it differentiates
+    any number of times; the tables take none."""
+
+    @staticmethod
+    def forward(ctx, u, tabs, terms, n_out, out_major=False):
+        ctx.tabs, ctx.terms, ctx.out_major, ctx.n_src = tabs, tuple(terms), bool(out_major), int(u.shape[1])
+        return _band_apply(u, None, tabs, ctx.terms, int(n_out), ctx.out_major)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.out_major:
+            g = g.transpose(0, 1)
+        adj = ctx.tabs.adj
+        back = tuple((o, s, c, a, 0 if a < 0 else adj[a][t]) for s, o, c, a, t in ctx.terms)
+        if any(a >= 0 and t is None for _, _, _, a, t in back):
+            raise RuntimeError("band apply: these tables carry no transpose")
+        return BandApplyFn.apply(g.float().contiguous(), ctx.tabs, back, ctx.n_src, False), None, None, None, None
+
+
+class SobolevSums:
+    """What one forward pass of a data loss leaves behind: the reduced loss (0-dim), the per-line norms and their
+    derivatives by the numerator sums (times the reduction factor)."""
+
+    def __init__(self, loss, v, dv):
+        self.loss, self.v, self.dv = loss, v, dv
+
+
+def _sobolev_desc(x, y, d, **cfg):
+    _require_gpu(x, "prediction")
+    _require_gpu(y, "target")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError(f"loss: prediction {tuple(x.shape)} on {x.device} against target {tuple(y.shape)} on {y.device}")
+    if x.dtype != torch.float32 or y.dtype != torch.float32 or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError("loss: contiguous fp32 operands")
+    if not 1 <= d <= 3 or x.dim() < d:
+        raise ValueError(f"loss: {d} spatial dims of a {x.dim()}-d tensor")
+    dims = tuple(int(n) for n in x.shape[x.dim() - d:])
+    lines = math.prod(int(n) for n in x.shape[:x.dim() - d])
+    tabs = cfg.pop("tabs", None)
+    if tabs is not None:
+        _require_gpu(tabs.t[0], "band tables")
+        if tabs.device != x.device or tabs.dims != dims:
+            raise ValueError(f"loss: tables for {tabs.dims} on {tabs.device}, field {dims} on {x.device}")
+        cfg["tabs"] = [t.data_ptr() for t in tabs.t]                  # row 0 of every axis: D
+        cfg["periodic"] = tabs.periodic
+    return _lib.ScEngineLib.sobolev_desc(dims=dims, lines=lines, **cfg), lines
+
+
+def sobolev_sums(x, y, d, **cfg):
+    """x, y (..., *dims) fp32 -> SobolevSums: stage 1 (partial sums per line and chunk) and stage 2 (the per-line norm,
+    its derivative, the reduced scalar) of LpLoss / H1Loss, two launches.  cfg: h1, p, relative, take_root, reduce_mean,
+    konst, eps, tabs (BandTables of kind "h1"), chunks."""
+    desc, lines = _sobolev_desc(x, y, d, **cfg)
+    lib = _lib.get_lib()
+    nbytes = lib.sobolev_workspace_bytes(desc)
+    if lines and not nbytes:
+        lib.sobolev_sums(desc, x.data_ptr(), y.data_ptr(), 0, 0, 0, 0, 0)          # raises with the engine's reason
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
+    out = torch.empty(2 * lines + 1, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        lib.sobolev_sums(desc, x.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes, out.data_ptr() + 4,
+                         out.data_ptr() + 4 * (1 + lines), out.data_ptr(), stream=_stream())
+    return SobolevSums(out[0], out[1:1 + lines], out[1 + lines:])
+
+
+def lp_grad(x, y, d, dv, gout, p):
+    """gx = dv[line] gout p |x - y|^(p-1) sign(x - y), shaped like x: one launch"""
+    desc, lines = _sobolev_desc(x, y, d, h1=False, p=p)
+    for t, what in ((dv, "dv"), (gout, "grad_output")):
+        _require_gpu(t, what)
+        if t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous():
+            raise ValueError(f"lp_grad: {what} must be contiguous fp32 on {x.device}")
+    if dv.numel() != lines or gout.numel() != 1:
+        raise ValueError("lp_grad: one dv per line, one grad_output")
+    gx = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.get_lib().lp_grad(desc, x.data_ptr(), y.data_ptr(), dv.data_ptr(), gout.data_ptr(), gx.data_ptr(),
+                               stream=_stream())
+    return gx
+
+
 class EngineOps:
     """The three local stages of a (mode-parallel) spectral layer on the MI355X engine."""
 
@@ -1024,6 +1259,15 @@ class EngineOps:
     @staticmethod
     def spectral_op(xhat, tabs, terms, n_out, conj=False, out_major=False):
         return SpectralOpFn.apply(xhat, tabs, terms, n_out, conj, out_major)
+
+    # banded real-space operators (differentiation.FiniteDiff) and the reductions of losses.LpLoss / H1Loss
+    @staticmethod
+    def band_apply(u, tabs, terms, n_out, out_major=False):
+        return BandApplyFn.apply(u, tabs, terms, n_out, out_major)
+
+    @staticmethod
+    def sobolev_sums(x, y, d, **cfg):
+        return sobolev_sums(x, y, d, **cfg)
 
     # one complex axis of a separable transform (the sharded dim of mpu.SpatialParallelSpectralConv):
     # x (B, L, n) complex -> (B, L, k) with kept row r reading FFT index rows[r], and its zero-padded inverse;
