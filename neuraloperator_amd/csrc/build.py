@@ -8,7 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libsc_engine.so")
 SOURCES = ["sc_engine.cpp"]
-# every kernel header next to the source (globbed: a new sc_kernels_*.h can not be forgotten here)
+# every header next to the source -- the kernels (sc_kernels_*.h) and the host parts sc_engine.cpp includes (sc_host_*.h);
+# globbed: a new one can not be forgotten here
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join("..", "..", "include", "sc_engine.h")]
 
 
