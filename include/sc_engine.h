@@ -367,6 +367,85 @@ int sc_sobolev_sums(const sc_sobolev_desc* desc, const float* x, const float* y,
 int sc_lp_grad(const sc_sobolev_desc* desc, const float* x, const float* y, const float* dv, const float* gout,
                float* gx, void* stream);
 
+/* ---- graph neural operator layer: radius search, CSR transpose, fused kernel integral, first layer by point ----
+ * All arrays contiguous; coordinates and features fp32, neighbour indices and splits int64 (the reference's dtypes).
+ * Every entry point refuses a bad descriptor before any launch (d outside 1..3, negative counts, null pointers,
+ * n_splits != rows + 1); m == 0, n == 0 or no edges are valid and launch nothing (owed outputs are zero-filled).
+ * Every index read from a caller's array is range-checked on the device before it addresses memory.  No float atomics:
+ * every sum runs in a fixed order.
+ *
+ * Fixed-radius search (neuralop/layers/neighbor_search.py:84-119, native_neighbor_search: the dense cdist, the two
+ * where(), nonzero() and the cumsum): data (n, d), queries (m, d), d = 1..3.  A pair is kept iff d2 <= r2, d2 =
+ * sum_k (q_k - p_k)^2 in fp32 in dimension order, r2 = (float)(radius * radius) formed in double; zero distances are
+ * kept (:104-107).  sc_radius_count writes deg[m] and row_splits[m + 1] (exclusive scan); the caller reads
+ * row_splits[m] -- ONE 8-byte copy, where the reference's nonzero() synchronises too -- to size the outputs of
+ * sc_radius_fill: index[n_edges], each query's neighbours in ascending data index (the nonzero() order), and with
+ * return_norm weights[n_edges] = d2, or 1e-14 where d2 == 0 (:105-111). */
+typedef struct {
+  int32_t d, return_norm;
+  int64_t n, m;
+  double radius;
+} sc_radius_desc;
+int sc_radius_count(const sc_radius_desc* desc, const float* data, const float* queries, int32_t* deg,
+                    int64_t* row_splits, void* stream);
+int sc_radius_fill(const sc_radius_desc* desc, const float* data, const float* queries, const int64_t* row_splits,
+                   int64_t n_edges, int64_t* index, float* weights, void* stream);
+
+/* Transpose of any valid CSR graph (rows, cols, n_edges; the backward pass of integral_transform.py:167 f_y[:, idx]):
+ * col_splits[cols + 1], perm[n_edges] = edge ids grouped by column, ascending within each group, row_of_edge[n_edges].
+ * Integer atomics build a histogram and fill slots; one wave per column then ranks its slice, so the output does not
+ * depend on their order.  ws: sc_csr_transpose_workspace_bytes. */
+typedef struct {
+  int64_t rows, cols, n_edges;
+  int64_t n_splits;                           /* entries of row_splits: must be rows + 1                    */
+} sc_csr_desc;
+size_t sc_csr_transpose_workspace_bytes(const sc_csr_desc* desc);
+int sc_csr_transpose(const sc_csr_desc* desc, const int64_t* row_splits, const int64_t* index, int64_t* col_splits,
+                     int32_t* perm, int32_t* row_of_edge, void* ws, size_t ws_bytes, void* stream);
+
+/* The fused kernel integral (integral_transform.py:167 gather, :198 mul_(in_features), :211 mul_(nbr_weights), :221
+ * segment_csr; segment_csr.py:63-98):
+ *   out[b, i, c] = s_i sum_{k in [splits[i], splits[i+1])} K[(b,) e, c] F[b, row(e), c] w[e] t(e),   e = perm[k] or k
+ * s_i = 1, or 1 / (segment length) with mean (an empty segment gives 0); F (b, n_f, c) and w [n_edges] optional;
+ * row(e) = gather64[e], gather32[e] or e; t(e) = 1 / (scale_splits[r + 1] - scale_splits[r]), r = gather32[e], where
+ * scale_splits is given (the mean of the ORIGINAL rows inside a transposed sum).  K (b, n_edges, c) or, with
+ * k_batch_stride 0, (n_edges, c); strides in floats.  One wave per (b, i) walks its segment in order.
+ * sc_csr_edge_grad, over the graph's own rows (no perm, no scale_splits):
+ *   gK[(b,) e, c] = s_i w[e] g[b, i, c] F[b, row(e), c],   summed over b inside the kernel when k_batch_stride is 0. */
+typedef struct {
+  int64_t rows, n_splits, n_edges;
+  int64_t n_f, n_scale_rows;
+  int64_t k_batch_stride, f_batch_stride;
+  int32_t channels, batch, mean, reserved;
+  const int64_t* splits;
+  const int32_t* perm;
+  const int64_t* gather64;
+  const int32_t* gather32;
+  const int64_t* scale_splits;
+  const float* w;
+} sc_csr_reduce_desc;
+int sc_csr_reduce(const sc_csr_reduce_desc* desc, const float* K, const float* F, float* out, void* stream);
+int sc_csr_edge_grad(const sc_csr_reduce_desc* desc, const float* g, const float* F, float* gK, void* stream);
+
+/* The first Linear of the kernel MLP by point instead of by edge (integral_transform.py:158-191: y[idx],
+ * repeat_interleave(x), the cat and fcs[0] of LinearChannelMLP, channel_mlp.py):
+ *   H[(b,) e, c] = act(Py[(b,) index[e], c] + Px[row(e), c] + bias[c]),   act = identity or GELU (erf)
+ * Py (b, n_py, c) or, with py_batch_stride 0, (n_py, c); Px (rows, c); H (batch, n_edges, c).  sc_edge_lift_bwd
+ * recomputes the pre-activation and writes gPre = gH act'(pre) in H's layout. */
+#define SC_LIFT_IDENTITY 0
+#define SC_LIFT_GELU 1
+typedef struct {
+  int64_t rows, n_splits, n_edges, n_py;
+  int64_t py_batch_stride;
+  int32_t channels, batch, act, reserved;
+  const int64_t* splits;
+  const int64_t* index;
+} sc_edge_lift_desc;
+int sc_edge_lift(const sc_edge_lift_desc* desc, const float* Py, const float* Px, const float* bias, float* H,
+                 void* stream);
+int sc_edge_lift_bwd(const sc_edge_lift_desc* desc, const float* Py, const float* Px, const float* bias,
+                     const float* gH, float* gPre, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -144,6 +144,31 @@ class SobolevDesc(Structure):                               # sc_sobolev_desc
                 ("lines", c_int64), ("konst", ctypes.c_double), ("eps", ctypes.c_double), ("T", c_void_p * 3)]
 
 
+class RadiusDesc(Structure):                                # sc_radius_desc
+    _fields_ = [("d", c_int32), ("return_norm", c_int32), ("n", c_int64), ("m", c_int64), ("radius", ctypes.c_double)]
+
+
+class CsrDesc(Structure):                                   # sc_csr_desc
+    _fields_ = [("rows", c_int64), ("cols", c_int64), ("n_edges", c_int64), ("n_splits", c_int64)]
+
+
+class CsrReduceDesc(Structure):                             # sc_csr_reduce_desc
+    _fields_ = [("rows", c_int64), ("n_splits", c_int64), ("n_edges", c_int64), ("n_f", c_int64),
+                ("n_scale_rows", c_int64), ("k_batch_stride", c_int64), ("f_batch_stride", c_int64),
+                ("channels", c_int32), ("batch", c_int32), ("mean", c_int32), ("reserved", c_int32),
+                ("splits", c_void_p), ("perm", c_void_p), ("gather64", c_void_p), ("gather32", c_void_p),
+                ("scale_splits", c_void_p), ("w", c_void_p)]
+
+
+class EdgeLiftDesc(Structure):                              # sc_edge_lift_desc
+    _fields_ = [("rows", c_int64), ("n_splits", c_int64), ("n_edges", c_int64), ("n_py", c_int64),
+                ("py_batch_stride", c_int64), ("channels", c_int32), ("batch", c_int32), ("act", c_int32),
+                ("reserved", c_int32), ("splits", c_void_p), ("index", c_void_p)]
+
+
+SC_LIFT_IDENTITY, SC_LIFT_GELU = 0, 1
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -203,7 +228,9 @@ class ScEngineLib:
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
                "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
                "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op",
-               "sc_band_apply", "sc_sobolev_workspace_bytes", "sc_sobolev_sums", "sc_lp_grad"]
+               "sc_band_apply", "sc_sobolev_workspace_bytes", "sc_sobolev_sums", "sc_lp_grad", "sc_radius_count",
+               "sc_radius_fill", "sc_csr_transpose_workspace_bytes", "sc_csr_transpose", "sc_csr_reduce",
+               "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -363,6 +390,18 @@ class ScEngineLib:
         L.sc_sobolev_sums.restype = c_int
         L.sc_lp_grad.argtypes = [POINTER(SobolevDesc)] + [c_void_p] * 6
         L.sc_lp_grad.restype = c_int
+        L.sc_radius_count.argtypes = [POINTER(RadiusDesc)] + [c_void_p] * 5
+        L.sc_radius_fill.argtypes = [POINTER(RadiusDesc), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+        L.sc_csr_transpose_workspace_bytes.argtypes = [POINTER(CsrDesc)]
+        L.sc_csr_transpose_workspace_bytes.restype = c_size_t
+        L.sc_csr_transpose.argtypes = [POINTER(CsrDesc)] + [c_void_p] * 6 + [c_size_t, c_void_p]
+        L.sc_csr_reduce.argtypes = [POINTER(CsrReduceDesc)] + [c_void_p] * 4
+        L.sc_csr_edge_grad.argtypes = [POINTER(CsrReduceDesc)] + [c_void_p] * 4
+        L.sc_edge_lift.argtypes = [POINTER(EdgeLiftDesc)] + [c_void_p] * 5
+        L.sc_edge_lift_bwd.argtypes = [POINTER(EdgeLiftDesc)] + [c_void_p] * 6
+        for s in ("sc_radius_count", "sc_radius_fill", "sc_csr_transpose", "sc_csr_reduce", "sc_csr_edge_grad",
+                  "sc_edge_lift", "sc_edge_lift_bwd"):
+            getattr(L, s).restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -718,6 +757,74 @@ class ScEngineLib:
         """gx[l, i] = dv[l] gout p |x - y|^(p-1) sign(x - y) (sc_lp_grad)"""
         self._check(self.lib.sc_lp_grad(byref(desc), x_ptr or None, y_ptr or None, dv_ptr or None, gout_ptr or None,
                                         gx_ptr or None, stream))
+
+    @staticmethod
+    def radius_desc(d, n, m, radius, return_norm=False):
+        r = RadiusDesc()
+        r.d, r.return_norm, r.n, r.m, r.radius = int(d), int(bool(return_norm)), int(n), int(m), float(radius)
+        return r
+
+    def radius_count(self, desc, data_ptr, queries_ptr, deg_ptr, splits_ptr, stream=0):
+        """deg[m] and the exclusive scan row_splits[m + 1] of a fixed-radius search (sc_radius_count)"""
+        self._check(self.lib.sc_radius_count(byref(desc), data_ptr or None, queries_ptr or None, deg_ptr or None,
+                                             splits_ptr or None, stream))
+
+    def radius_fill(self, desc, data_ptr, queries_ptr, splits_ptr, n_edges, index_ptr, weights_ptr, stream=0):
+        """neighbors_index[n_edges] (ascending per query) and the squared distances (sc_radius_fill)"""
+        self._check(self.lib.sc_radius_fill(byref(desc), data_ptr or None, queries_ptr or None, splits_ptr or None,
+                                            n_edges, index_ptr or None, weights_ptr or None, stream))
+
+    @staticmethod
+    def csr_desc(rows, cols, n_edges, n_splits=None):
+        d = CsrDesc()
+        d.rows, d.cols, d.n_edges = int(rows), int(cols), int(n_edges)
+        d.n_splits = int(rows) + 1 if n_splits is None else int(n_splits)
+        return d
+
+    def csr_transpose_workspace_bytes(self, desc):
+        return int(self.lib.sc_csr_transpose_workspace_bytes(byref(desc)))
+
+    def csr_transpose(self, desc, splits_ptr, index_ptr, col_splits_ptr, perm_ptr, row_ptr, ws_ptr, ws_bytes, stream=0):
+        self._check(self.lib.sc_csr_transpose(byref(desc), splits_ptr or None, index_ptr or None, col_splits_ptr or None,
+                                              perm_ptr or None, row_ptr or None, ws_ptr or None, ws_bytes, stream))
+
+    @staticmethod
+    def csr_reduce_desc(*, rows, n_edges, channels, splits, n_splits=None, batch=1, mean=False, n_f=0, n_scale_rows=0,
+                        k_batch_stride=0, f_batch_stride=0, perm=0, gather64=0, gather32=0, scale_splits=0, w=0):
+        d = CsrReduceDesc()
+        d.rows, d.n_edges, d.channels, d.batch, d.mean = int(rows), int(n_edges), int(channels), int(batch), int(bool(mean))
+        d.n_splits = int(rows) + 1 if n_splits is None else int(n_splits)
+        d.n_f, d.n_scale_rows, d.k_batch_stride, d.f_batch_stride = int(n_f), int(n_scale_rows), int(k_batch_stride), int(f_batch_stride)
+        d.splits, d.perm, d.gather64, d.gather32 = splits or None, perm or None, gather64 or None, gather32 or None
+        d.scale_splits, d.w = scale_splits or None, w or None
+        return d
+
+    def csr_reduce(self, desc, k_ptr, f_ptr, out_ptr, stream=0):
+        """out[b, i] = s_i sum over the segment of K F w (sc_csr_reduce)"""
+        self._check(self.lib.sc_csr_reduce(byref(desc), k_ptr or None, f_ptr or None, out_ptr or None, stream))
+
+    def csr_edge_grad(self, desc, g_ptr, f_ptr, gk_ptr, stream=0):
+        """gK[(b,) e] = s_i w[e] g[b, i] F[b, row(e)] (sc_csr_edge_grad)"""
+        self._check(self.lib.sc_csr_edge_grad(byref(desc), g_ptr or None, f_ptr or None, gk_ptr or None, stream))
+
+    @staticmethod
+    def edge_lift_desc(*, rows, n_edges, n_py, channels, splits, index, batch=1, py_batch_stride=0, act=SC_LIFT_IDENTITY,
+                       n_splits=None):
+        d = EdgeLiftDesc()
+        d.rows, d.n_edges, d.n_py, d.channels, d.batch, d.act = int(rows), int(n_edges), int(n_py), int(channels), int(batch), int(act)
+        d.n_splits = int(rows) + 1 if n_splits is None else int(n_splits)
+        d.py_batch_stride, d.splits, d.index = int(py_batch_stride), splits or None, index or None
+        return d
+
+    def edge_lift(self, desc, py_ptr, px_ptr, bias_ptr, h_ptr, stream=0):
+        """H[(b,) e] = act(Py[(b,) index[e]] + Px[row(e)] + bias) (sc_edge_lift)"""
+        self._check(self.lib.sc_edge_lift(byref(desc), py_ptr or None, px_ptr or None, bias_ptr or None, h_ptr or None,
+                                          stream))
+
+    def edge_lift_bwd(self, desc, py_ptr, px_ptr, bias_ptr, gh_ptr, gpre_ptr, stream=0):
+        """gPre = gH act'(pre), the pre-activation recomputed (sc_edge_lift_bwd)"""
+        self._check(self.lib.sc_edge_lift_bwd(byref(desc), py_ptr or None, px_ptr or None, bias_ptr or None,
+                                              gh_ptr or None, gpre_ptr or None, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

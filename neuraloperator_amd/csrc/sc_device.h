@@ -115,6 +115,12 @@ SC_DEVICE void sc_swap32(float& a, float& b) {
 
 // float add into LDS shared by the waves of a workgroup: ds_add_f32 (no return value)
 #define SC_LDS_ADD(ptr, val) atomicAdd((ptr), (val))
+// integer add to global memory, the old value returned (sc_kernels_gno.h: histogram and slot counters whose final
+// content does not depend on the order of the adds)
+#define SC_ATOMIC_ADD_I32(ptr, val) atomicAdd((ptr), (val))
+// one bit per lane of the wave: the lanes whose predicate holds (v_cmp into an SGPR pair), and a 64-bit population count
+SC_DEVICE unsigned long long sc_ballot(const bool p) { return __builtin_amdgcn_ballot_w64(p); }
+SC_DEVICE int sc_popc64(const unsigned long long m) { return __popcll(m); }
 
 typedef hipStream_t sc_stream_t;
 
@@ -282,6 +288,19 @@ inline void sc_emu_lds_add(float* p, const float v) {
   } while (!__atomic_compare_exchange_n(u, &old, nw, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED));
 }
 #define SC_LDS_ADD(ptr, val) sc_emu_lds_add((ptr), (val))
+#define SC_ATOMIC_ADD_I32(ptr, val) __atomic_fetch_add((ptr), (val), __ATOMIC_RELAXED)
+// the wave's ballot through the per-wave scratch between two wave rendezvous (every lane of the wave must reach it)
+inline unsigned long long sc_ballot(const bool p) {
+  float* s = scemu::wave_scratch();
+  s[SC_TID & 63] = p ? 1.f : 0.f;
+  scemu::wave_barrier();
+  unsigned long long m = 0;
+  for (int i = 0; i < 64; ++i)
+    if (s[i] != 0.f) m |= 1ull << i;
+  scemu::wave_barrier();
+  return m;
+}
+inline int sc_popc64(const unsigned long long m) { return __builtin_popcountll(m); }
 
 // capture the arguments by value in a lambda and hand it to the thread pool
 #define SC_LAUNCH(kernel, grid, block, shmem, stream, ...)                          \

@@ -51,6 +51,7 @@
 #include "sc_kernels_wire.h"
 #include "sc_host_common.h"
 #include "sc_host_modegemm.h"
+#include "sc_host_gno.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

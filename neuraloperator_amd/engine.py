@@ -1221,6 +1221,235 @@ def lp_grad(x, y, d, dv, gout, p):
     return gx
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# graph neural operator layer (sc_kernels_gno.h): radius search, CSR transpose, fused kernel integral, first layer by point
+# ---------------------------------------------------------------------------------------------------------------------
+def _gno_tensor(t, what, dtype=torch.float32, device=None):
+    _require_gpu(t, what)
+    if t.dtype != dtype:
+        raise ValueError(f"gno: {what} must be {dtype}, got {t.dtype}")
+    if device is not None and t.device != device:
+        raise ValueError(f"gno: {what} on {t.device}, expected {device}")
+    return t.contiguous()
+
+
+def radius_search(data, queries, radius, return_norm=False):
+    """Fixed-radius neighbours of every query among data (n, d), d = 1..3, as the reference's dict: neighbors_index
+    int64 [E] (ascending per query), neighbors_row_splits int64 [m + 1], with return_norm weights fp32 [E] (squared
+    distances, 1e-14 for coincident points).  Two passes (count + scan, fill); between them the host reads the edge
+    count -- one 8-byte copy, where the reference's nonzero() synchronises too."""
+    data = _gno_tensor(data.detach(), "data")
+    queries = _gno_tensor(queries.detach(), "queries", device=data.device)
+    if data.dim() != 2 or queries.dim() != 2 or data.shape[1] != queries.shape[1] or not 1 <= data.shape[1] <= 3:
+        raise ValueError(f"neighbor search: data {tuple(data.shape)} and queries {tuple(queries.shape)} must be "
+                         "(n, d) and (m, d) with d = 1, 2 or 3")
+    n, m, dev = int(data.shape[0]), int(queries.shape[0]), data.device
+    lib = _lib.get_lib()
+    desc = lib.radius_desc(data.shape[1], n, m, radius, return_norm)
+    deg = torch.empty(m, dtype=torch.int32, device=dev)
+    splits = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        lib.radius_count(desc, data.data_ptr(), queries.data_ptr(), deg.data_ptr(), splits.data_ptr(), stream=_stream())
+        n_edges = int(splits[m].item())
+        index = torch.empty(n_edges, dtype=torch.int64, device=dev)
+        weights = torch.empty(n_edges, dtype=torch.float32, device=dev) if return_norm else None
+        lib.radius_fill(desc, data.data_ptr(), queries.data_ptr(), splits.data_ptr(), n_edges, index.data_ptr(),
+                        0 if weights is None else weights.data_ptr(), stream=_stream())
+    out = {}
+    if return_norm:
+        out["weights"] = weights
+    out["neighbors_index"] = index
+    out["neighbors_row_splits"] = splits
+    return out
+
+
+class CsrGraph:
+    """A neighbour graph in CSR form (rows = queries, columns = data points) and, built on first use by a backward pass
+    and kept, its transpose: col_splits int64 [cols + 1], perm int32 [E] (edge ids by column, ascending), row_of_edge
+    int32 [E].  Any valid CSR: the arrays may come from a caller, not from radius_search."""
+
+    def __init__(self, splits, index, cols, n_edges=None):
+        self.splits = _gno_tensor(splits, "neighbors_row_splits", torch.int64)
+        # index None: segments only (segment_csr), n_edges given
+        self.index = None if index is None else _gno_tensor(index, "neighbors_index", torch.int64, self.splits.device)
+        if self.splits.dim() != 1 or self.splits.numel() < 1 or (index is not None and self.index.dim() != 1):
+            raise ValueError("gno: neighbors_row_splits [m + 1] and neighbors_index [E] must be 1-d")
+        self.rows, self.cols = self.splits.numel() - 1, int(cols)
+        self.n_edges = int(n_edges) if index is None else self.index.numel()
+        self.device = self.splits.device
+        self._t = None
+
+    def transpose(self):
+        if self._t is None:
+            lib, dev = _lib.get_lib(), self.device
+            desc = lib.csr_desc(self.rows, self.cols, self.n_edges)
+            nbytes = lib.csr_transpose_workspace_bytes(desc)
+            ws = _ws(nbytes, dev)
+            col_splits = torch.empty(self.cols + 1, dtype=torch.int64, device=dev)
+            perm = torch.empty(self.n_edges, dtype=torch.int32, device=dev)
+            row = torch.empty(self.n_edges, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                lib.csr_transpose(desc, self.splits.data_ptr(), self.index.data_ptr(), col_splits.data_ptr(),
+                                  perm.data_ptr(), row.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+            self._t = (col_splits, perm, row)
+        return self._t
+
+
+def _csr_reduce(graph, K, F=None, w=None, mean=False, transposed=False):
+    """K (E, c) or (b, E, c), F None, (nF, c) or (b, nF, c) -> (rows, c) or (b, rows, c), batched where K or F is.
+    transposed: the segments are the graph's columns, F is read at the edge's row, mean scales by the ROW's degree."""
+    dev = graph.device
+    K = _gno_tensor(K, "edge values", device=dev)
+    kb = K.dim() == 3
+    c = int(K.shape[-1])
+    fb = F is not None and F.dim() == 3
+    if F is not None:
+        F = _gno_tensor(F, "point values", device=dev)
+    if w is not None:
+        w = _gno_tensor(w, "edge weights", device=dev)
+        if w.numel() != graph.n_edges:
+            raise ValueError(f"gno: {w.numel()} edge weights for {graph.n_edges} edges")
+    batch = int(K.shape[0]) if kb else (int(F.shape[0]) if fb else 1)
+    if K.shape[-2] != graph.n_edges or (kb and fb and K.shape[0] != F.shape[0]) or (F is not None and F.shape[-1] != c):
+        raise ValueError(f"gno: edge values {tuple(K.shape)} against {graph.n_edges} edges"
+                         + ("" if F is None else f" and point values {tuple(F.shape)}"))
+    if transposed:
+        col_splits, perm, row = graph.transpose()
+        rows, splits = graph.cols, col_splits
+        kw = dict(perm=perm.data_ptr(), gather32=row.data_ptr(), n_scale_rows=graph.rows,
+                  scale_splits=graph.splits.data_ptr() if mean else 0)
+        need = graph.rows
+    else:
+        rows, splits = graph.rows, graph.splits
+        kw = dict(gather64=graph.index.data_ptr() if F is not None else 0, mean=mean)
+        need = graph.cols
+    if F is not None and F.shape[-2] != need:
+        raise ValueError(f"gno: point values {tuple(F.shape)} against {need} points")
+    lib = _lib.get_lib()
+    desc = lib.csr_reduce_desc(rows=rows, n_edges=graph.n_edges, channels=c, splits=splits.data_ptr(), batch=batch,
+                               n_f=0 if F is None else need, k_batch_stride=graph.n_edges * c if kb else 0,
+                               f_batch_stride=need * c if fb else 0, w=0 if w is None else w.data_ptr(), **kw)
+    out = torch.empty((batch, rows, c) if (kb or fb) else (rows, c), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.csr_reduce(desc, K.data_ptr(), 0 if F is None else F.data_ptr(), out.data_ptr(), stream=_stream())
+    return out
+
+
+def _csr_edge_grad(graph, g, F, w, mean, k_batched):
+    """gK (E, c), or (b, E, c) with k_batched, from g (rows, c) / (b, rows, c) and F None / (n, c) / (b, n, c)"""
+    dev = graph.device
+    g = _gno_tensor(g, "output gradient", device=dev)
+    gb = g.dim() == 3
+    batch, c = (int(g.shape[0]) if gb else 1), int(g.shape[-1])
+    fb = F is not None and F.dim() == 3
+    if F is not None:
+        F = _gno_tensor(F, "point values", device=dev)
+    lib = _lib.get_lib()
+    desc = lib.csr_reduce_desc(rows=graph.rows, n_edges=graph.n_edges, channels=c, splits=graph.splits.data_ptr(),
+                               batch=batch, mean=mean, n_f=0 if F is None else graph.cols,
+                               k_batch_stride=graph.n_edges * c if k_batched else 0,
+                               f_batch_stride=graph.cols * c if fb else 0,
+                               gather64=graph.index.data_ptr() if F is not None else 0, w=0 if w is None else w.data_ptr())
+    gK = torch.empty((batch, graph.n_edges, c) if k_batched else (graph.n_edges, c), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.csr_edge_grad(desc, g.data_ptr(), 0 if F is None else F.data_ptr(), gK.data_ptr(), stream=_stream())
+    return gK
+
+
+class KernelIntegralFn(torch.autograd.Function):
+    """out[b, i] = s_i sum_{e in row i} K[(b,) e] F[b, index[e]] w[e] (sc_csr_reduce): the gather, the two products
+    and the segment reduction of the reference's IntegralTransform in one launch.  Backward: gK is one sc_csr_edge_grad,
+    gF one sc_csr_reduce over the transposed graph.  The weights take no gradient."""
+
+    @staticmethod
+    def forward(ctx, K, F, graph, w, mean):
+        ctx.graph, ctx.mean, ctx.w = graph, bool(mean), w
+        ctx.k_batched = K.dim() == 3
+        ctx.f_shape = None if F is None else tuple(F.shape)
+        ctx.save_for_backward(K, F)
+        return _csr_reduce(graph, K, F, w, mean)
+
+    @staticmethod
+    def backward(ctx, g):
+        K, F = ctx.saved_tensors
+        g = g.float().contiguous()
+        gK = gF = None
+        if ctx.needs_input_grad[0]:
+            gK = _csr_edge_grad(ctx.graph, g, F, ctx.w, ctx.mean, ctx.k_batched)
+        if F is not None and ctx.needs_input_grad[1]:
+            gF = _csr_reduce(ctx.graph, K, g, ctx.w, ctx.mean, transposed=True)
+            if len(ctx.f_shape) == 2 and gF.dim() == 3:
+                gF = gF.sum(0)
+        return gK, gF, None, None, None
+
+
+class EdgeLiftFn(torch.autograd.Function):
+    """H[(b,) e] = act(Py[(b,) index[e]] + Px[row(e)] + bias) (sc_edge_lift): the first Linear of the kernel MLP split
+    by column blocks, so that neither cat[y[idx], x_rep, f_y[idx]] nor the per-edge product is formed.  Backward:
+    sc_edge_lift_bwd recomputes the pre-activation; gPy is one transposed sc_csr_reduce, gPx one row-wise one, gbias
+    its column sum."""
+
+    @staticmethod
+    def forward(ctx, Py, Px, bias, graph, gelu):
+        dev = graph.device
+        Py, Px = _gno_tensor(Py, "Py", device=dev), _gno_tensor(Px, "Px", device=dev)
+        if bias is not None:
+            bias = _gno_tensor(bias, "bias", device=dev)
+        c = int(Px.shape[-1])
+        if Px.shape != (graph.rows, c) or Py.shape[-2:] != (graph.cols, c) or (bias is not None and bias.shape != (c,)):
+            raise ValueError(f"gno: lift of Py {tuple(Py.shape)}, Px {tuple(Px.shape)} on a graph of {graph.rows} rows, "
+                             f"{graph.cols} columns")
+        ctx.graph, ctx.gelu = graph, bool(gelu)
+        ctx.save_for_backward(Py, Px, bias)
+        H = torch.empty((*Py.shape[:-2], graph.n_edges, c), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.get_lib().edge_lift(EdgeLiftFn._desc(ctx, Py), Py.data_ptr(), Px.data_ptr(),
+                                     0 if bias is None else bias.data_ptr(), H.data_ptr(), stream=_stream())
+        return H
+
+    @staticmethod
+    def _desc(ctx, Py):
+        g, pb = ctx.graph, Py.dim() == 3
+        return _lib.ScEngineLib.edge_lift_desc(
+            rows=g.rows, n_edges=g.n_edges, n_py=g.cols, channels=int(Py.shape[-1]), splits=g.splits.data_ptr(),
+            index=g.index.data_ptr(), batch=int(Py.shape[0]) if pb else 1,
+            py_batch_stride=g.cols * int(Py.shape[-1]) if pb else 0,
+            act=_lib.SC_LIFT_GELU if ctx.gelu else _lib.SC_LIFT_IDENTITY)
+
+    @staticmethod
+    def backward(ctx, gH):
+        Py, Px, bias = ctx.saved_tensors
+        gH = gH.float().contiguous()
+        gPre = torch.empty_like(gH)
+        with torch.cuda.device(gH.device):
+            _lib.get_lib().edge_lift_bwd(EdgeLiftFn._desc(ctx, Py), Py.data_ptr(), Px.data_ptr(),
+                                         0 if bias is None else bias.data_ptr(), gH.data_ptr(), gPre.data_ptr(),
+                                         stream=_stream())
+        gPy = gPx = gb = None
+        if ctx.needs_input_grad[0]:
+            gPy = _csr_reduce(ctx.graph, gPre, transposed=True)
+        if ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2]):
+            gPx = _csr_reduce(ctx.graph, gPre)
+            if gPx.dim() == 3:
+                gPx = gPx.sum(0)
+            if bias is not None and ctx.needs_input_grad[2]:
+                gb = gPx.sum(0)
+        return gPy, gPx, gb, None, None
+
+
+class SegmentCsrFn(torch.autograd.Function):
+    """out[(b,) i] = sum (or mean) of src[(b,) e] over row i (sc_csr_reduce with K = src)"""
+
+    @staticmethod
+    def forward(ctx, src, graph, mean):
+        ctx.graph, ctx.mean, ctx.batched = graph, bool(mean), src.dim() == 3
+        return _csr_reduce(graph, src, mean=mean)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _csr_edge_grad(ctx.graph, g.float().contiguous(), None, None, ctx.mean, ctx.batched), None, None
+
+
 class EngineOps:
     """The three local stages of a (mode-parallel) spectral layer on the MI355X engine."""
 

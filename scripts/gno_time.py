@@ -1,0 +1,110 @@
+"""The graph neural operator layer on one MI355X, for manual use (no test runs this):
+
+    python scripts/gno_time.py [--iters 50] [--out profiles/gno.txt]
+
+Per shape: the engine's radius search, first layer by point (sc_edge_lift) and fused reduce (sc_csr_reduce), each beside
+a device-to-device copy of its own algorithmic bytes, and a whole GNOBlock forward + backward beside the reference's
+formula written as a torch chain on the same GPU (dense cdist search, indexing, the MLP over edges, index_add_ in place of
+the Python loop of segment_csr).  Shapes: 3586 surface points against 32^3 and 64^3 grid queries at radius 0.033 (the
+GINO in direction) and the reverse (the out direction).  Events around the whole loop after a warm-up."""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from neuraloperator_amd import GNOBlock, engine  # noqa: E402
+
+N_SURF, RADIUS, CH = 3586, 0.033, 32
+
+
+def timed(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters * 1e3          # us
+
+
+def copy_us(nbytes, iters):
+    n = max(int(nbytes) // 8, 1)                    # a copy reads and writes every byte once
+    src, dst = torch.empty(n, dtype=torch.float32, device="cuda"), torch.empty(n, dtype=torch.float32, device="cuda")
+    return timed(lambda: dst.copy_(src), iters)
+
+
+def chain_search(data, queries, radius):
+    d = torch.cdist(queries, data)
+    hit = d <= radius
+    return {"neighbors_index": hit.nonzero()[:, 1], "neighbors_row_splits": F.pad(hit.sum(1).cumsum(0), (1, 0))}
+
+
+def chain_block(block, y, x, f, chunk=8192):
+    """the reference's formula, dense search in query chunks so that 64^3 x 3586 distances fit"""
+    idx, rows = [], []
+    for q0 in range(0, x.shape[0], chunk):
+        hit = (torch.cdist(x[q0:q0 + chunk], y) <= block.radius).nonzero()
+        rows.append(hit[:, 0] + q0)
+        idx.append(hit[:, 1])
+    idx, rows = torch.cat(idx), torch.cat(rows)
+    ye, xe = block.pos_embedding(y), block.pos_embedding(x)
+    k = block.integral_transform.channel_mlp(torch.cat([ye[idx], xe[rows]], -1)) * f[:, idx]
+    return torch.zeros(f.shape[0], x.shape[0], k.shape[-1], device=k.device).index_add_(1, rows, k)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    surf = (0.25 + 0.5 * torch.rand(N_SURF, 3, generator=g)).to(dev)
+    lines = [f"{'shape':>22s} {'step':>14s} {'engine us':>10s} {'copy us':>9s} {'torch chain us':>15s}"]
+    for res in (32, 64):
+        ax = torch.linspace(0, 1, res)
+        grid = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3).to(dev)
+        for tag, y, x in ((f"in {N_SURF}->{res}^3", surf, grid), (f"out {res}^3->{N_SURF}", grid, surf)):
+            n, m = y.shape[0], x.shape[0]
+            nb = engine.radius_search(y, x, RADIUS)
+            E = nb["neighbors_index"].numel()
+            graph = engine.CsrGraph(nb["neighbors_row_splits"], nb["neighbors_index"], n)
+            rows = [("search", timed(lambda: engine.radius_search(y, x, RADIUS), args.iters),
+                     copy_us(12 * (n + m) + 8 * (m + 1) + 8 * E, args.iters),
+                     timed(lambda: chain_search(y, x, RADIUS), args.iters) if m * n < 2 ** 28 else float("nan"))]
+            h = 128
+            Py, Px, b = torch.randn(n, h, device=dev), torch.randn(m, h, device=dev), torch.randn(h, device=dev)
+            rows.append(("lift h=128", timed(lambda: engine.EdgeLiftFn.apply(Py, Px, b, graph, True), args.iters),
+                         copy_us(4 * h * (n + m + E) + 8 * E, args.iters), float("nan")))
+            K, Fv = torch.randn(E, CH, device=dev), torch.randn(1, n, CH, device=dev)
+            rows.append(("reduce c=32", timed(lambda: engine._csr_reduce(graph, K, Fv), args.iters),
+                         copy_us(4 * CH * (E + n + m) + 8 * E, args.iters), float("nan")))
+            block = GNOBlock(CH, CH, 3, RADIUS, channel_mlp_layers=[128, 256, 128]).to(dev)
+            f = torch.randn(1, n, CH, device=dev, requires_grad=True)
+
+            def step(fn):
+                f.grad = None
+                block.zero_grad(set_to_none=True)
+                fn().sum().backward()
+            rows.append(("block fwd+bwd", timed(lambda: step(lambda: block(y, x, f)), args.iters), float("nan"),
+                         timed(lambda: step(lambda: chain_block(block, y, x, f)), max(args.iters // 5, 2))))
+            for name, t_eng, t_copy, t_ref in rows:
+                lines.append(f"{tag:>22s} {name:>14s} {t_eng:10.1f} {t_copy:9.1f} {t_ref:15.1f}")
+                print(lines[-1], flush=True)
+            lines.append(f"{tag:>22s} {'edges':>14s} {E:10d}")
+    text = "\n".join(lines) + "\n"
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
