@@ -446,6 +446,42 @@ int sc_edge_lift(const sc_edge_lift_desc* desc, const float* Py, const float* Px
 int sc_edge_lift_bwd(const sc_edge_lift_desc* desc, const float* Py, const float* Px, const float* bias,
                      const float* gH, float* gPre, void* stream);
 
+/* ---- finite-difference convolution of the local neural operator (neuralop/layers/differential_conv.py:6-101) ----
+ *   y = (conv_pad(x, W) - conv_1x1(x, sum_taps W)) * inv_h
+ * as ONE convolution with folded weights: W'[.., t] = W[.., t] inv_h off the centre, W'[.., centre] = -(sum of the other
+ * taps) inv_h.  x (batch, c_in, dims[0..ndim-1]), W (c_out, c_in / groups, k..k), y (batch, c_out, dims..), all fp32
+ * contiguous; k in {3, 5, 7}; padding as below (the reference's periodic / zeros / replicate / reflect).
+ * sc_fdconv_backward writes gx (like x), gw (like W; its centre tap is exactly 0), or both -- a null pointer means not
+ * wanted: gx is the adjoint of padding followed by the convolution, gw[.., t] = (G[.., t] - G[.., centre]) inv_h with
+ * G[o, c, t] = sum_{b, p} gout[b, o, p] xpad[b, c, p + t].  x may be null when gw is, w when gx is.
+ * The backward call needs sc_fdconv_workspace_bytes(desc) bytes (the folded weights, the partial sums of gw, the padded
+ * data gradient of replicate / reflect), the forward call sc_fdconv_forward_workspace_bytes(desc) (the folded weights
+ * alone; a workspace of the larger size serves both).  Refused before any launch: an even k, k outside 3..7, groups that do not divide both
+ * channel counts, reflect with an extent <= k / 2, periodic with an extent < k / 2, a null pointer, a small workspace.
+ * sc_fdconv_path: the route a descriptor takes (0 = refused) -- SC_FDCONV_PATH_MFMA for groups = 1, ndim = 2, k = 3,
+ * c_in, c_out in {32, 64, 128}, periodic or zeros (implicit GEMM on the exact-fp32 matrix instruction), the vector-ALU
+ * route otherwise.  Deterministic: no float atomics, every sum in a fixed order that depends on the descriptor alone. */
+#define SC_FDCONV_PERIODIC 0
+#define SC_FDCONV_ZEROS 1
+#define SC_FDCONV_REPLICATE 2
+#define SC_FDCONV_REFLECT 3
+#define SC_FDCONV_PATH_GENERAL 1
+#define SC_FDCONV_PATH_MFMA 2
+typedef struct {
+  int32_t ndim, k, padding, groups;
+  int64_t dims[3];
+  int64_t batch, c_in, c_out;
+  float inv_h;
+  int32_t reserved;
+} sc_fdconv_desc;
+int sc_fdconv_path(const sc_fdconv_desc* desc);
+size_t sc_fdconv_workspace_bytes(const sc_fdconv_desc* desc);
+size_t sc_fdconv_forward_workspace_bytes(const sc_fdconv_desc* desc);
+int sc_fdconv_forward(const sc_fdconv_desc* desc, const float* x, const float* w, float* y, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int sc_fdconv_backward(const sc_fdconv_desc* desc, const float* x, const float* w, const float* gout, float* gx,
+                       float* gw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

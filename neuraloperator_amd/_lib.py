@@ -169,6 +169,16 @@ class EdgeLiftDesc(Structure):                              # sc_edge_lift_desc
 SC_LIFT_IDENTITY, SC_LIFT_GELU = 0, 1
 
 
+class FdconvDesc(Structure):                                # sc_fdconv_desc
+    _fields_ = [("ndim", c_int32), ("k", c_int32), ("padding", c_int32), ("groups", c_int32), ("dims", c_int64 * 3),
+                ("batch", c_int64), ("c_in", c_int64), ("c_out", c_int64), ("inv_h", ctypes.c_float),
+                ("reserved", c_int32)]
+
+
+SC_FDCONV_PADDING = {"periodic": 0, "zeros": 1, "replicate": 2, "reflect": 3}
+SC_FDCONV_PATH_GENERAL, SC_FDCONV_PATH_MFMA = 1, 2
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -230,7 +240,9 @@ class ScEngineLib:
                "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op",
                "sc_band_apply", "sc_sobolev_workspace_bytes", "sc_sobolev_sums", "sc_lp_grad", "sc_radius_count",
                "sc_radius_fill", "sc_csr_transpose_workspace_bytes", "sc_csr_transpose", "sc_csr_reduce",
-               "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd"]
+               "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd", "sc_fdconv_path", "sc_fdconv_workspace_bytes",
+               "sc_fdconv_forward_workspace_bytes",
+               "sc_fdconv_forward", "sc_fdconv_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -402,6 +414,16 @@ class ScEngineLib:
         for s in ("sc_radius_count", "sc_radius_fill", "sc_csr_transpose", "sc_csr_reduce", "sc_csr_edge_grad",
                   "sc_edge_lift", "sc_edge_lift_bwd"):
             getattr(L, s).restype = c_int
+        L.sc_fdconv_path.argtypes = [POINTER(FdconvDesc)]
+        L.sc_fdconv_path.restype = c_int
+        L.sc_fdconv_workspace_bytes.argtypes = [POINTER(FdconvDesc)]
+        L.sc_fdconv_workspace_bytes.restype = c_size_t
+        L.sc_fdconv_forward_workspace_bytes.argtypes = [POINTER(FdconvDesc)]
+        L.sc_fdconv_forward_workspace_bytes.restype = c_size_t
+        L.sc_fdconv_forward.argtypes = [POINTER(FdconvDesc)] + [c_void_p] * 4 + [c_size_t, c_void_p]
+        L.sc_fdconv_forward.restype = c_int
+        L.sc_fdconv_backward.argtypes = [POINTER(FdconvDesc)] + [c_void_p] * 6 + [c_size_t, c_void_p]
+        L.sc_fdconv_backward.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -825,6 +847,37 @@ class ScEngineLib:
         """gPre = gH act'(pre), the pre-activation recomputed (sc_edge_lift_bwd)"""
         self._check(self.lib.sc_edge_lift_bwd(byref(desc), py_ptr or None, px_ptr or None, bias_ptr or None,
                                               gh_ptr or None, gpre_ptr or None, stream))
+
+    @staticmethod
+    def fdconv_desc(*, dims, batch, c_in, c_out, k, groups=1, padding="periodic", inv_h=1.0):
+        d = FdconvDesc()
+        d.ndim, d.k, d.groups = len(dims), int(k), int(groups)
+        d.padding = SC_FDCONV_PADDING[padding] if isinstance(padding, str) else int(padding)
+        for i, n in enumerate(dims[:3]):
+            d.dims[i] = int(n)
+        d.batch, d.c_in, d.c_out, d.inv_h = int(batch), int(c_in), int(c_out), float(inv_h)
+        return d
+
+    def fdconv_path(self, desc):
+        """the route of a descriptor: SC_FDCONV_PATH_GENERAL, SC_FDCONV_PATH_MFMA, or 0 where it is refused"""
+        return int(self.lib.sc_fdconv_path(byref(desc)))
+
+    def fdconv_workspace_bytes(self, desc):
+        return int(self.lib.sc_fdconv_workspace_bytes(byref(desc)))
+
+    def fdconv_forward_workspace_bytes(self, desc):
+        """what sc_fdconv_forward needs: the folded weights alone"""
+        return int(self.lib.sc_fdconv_forward_workspace_bytes(byref(desc)))
+
+    def fdconv_forward(self, desc, x_ptr, w_ptr, y_ptr, ws_ptr, ws_bytes, stream=0):
+        """y = (conv_pad(x, W) - conv_1x1(x, sum_taps W)) inv_h as one folded convolution (sc_fdconv_forward)"""
+        self._check(self.lib.sc_fdconv_forward(byref(desc), x_ptr or None, w_ptr or None, y_ptr or None, ws_ptr or None,
+                                               ws_bytes, stream))
+
+    def fdconv_backward(self, desc, x_ptr, w_ptr, gout_ptr, gx_ptr, gw_ptr, ws_ptr, ws_bytes, stream=0):
+        """gx and / or gw of sc_fdconv_forward (a zero pointer: not wanted)"""
+        self._check(self.lib.sc_fdconv_backward(byref(desc), x_ptr or None, w_ptr or None, gout_ptr or None,
+                                                gx_ptr or None, gw_ptr or None, ws_ptr or None, ws_bytes, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

@@ -52,6 +52,7 @@
 #include "sc_host_common.h"
 #include "sc_host_modegemm.h"
 #include "sc_host_gno.h"
+#include "sc_host_fdconv.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

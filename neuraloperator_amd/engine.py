@@ -1515,6 +1515,58 @@ class EngineOps:
         return BicubicRowsFn.apply(x, list(in_grid), list(out_grid), int(src_row0), int(out_row0), int(out_rows))
 
 
+class FdConvFn(torch.autograd.Function):
+    """y = (conv_pad(x, W) - conv_1x1(x, sum_taps W)) / grid_width as one folded convolution (sc_fdconv_forward);
+    backward: one sc_fdconv_backward call writes gx, gW or both.  x (B, C_in, d..) fp32, weight (C_out, C_in / groups,
+    k..k) fp32; padding one of periodic / zeros / replicate / reflect; grid_width a plain number."""
+
+    @staticmethod
+    def desc(x, weight, groups, padding, grid_width):
+        k = int(weight.shape[-1])
+        return _lib.ScEngineLib.fdconv_desc(dims=[int(s) for s in x.shape[2:]], batch=int(x.shape[0]),
+                                            c_in=int(x.shape[1]), c_out=int(weight.shape[0]), k=k, groups=int(groups),
+                                            padding=padding, inv_h=1.0 / float(grid_width))
+
+    @staticmethod
+    def forward(ctx, x, weight, groups, padding, grid_width):
+        _require_gpu(x)
+        _require_gpu(weight, "weight")
+        if x.dtype != torch.float32 or weight.dtype != torch.float32:
+            raise ValueError(f"fdconv: float32 tensors, got {x.dtype} and {weight.dtype}")
+        nd = x.dim() - 2
+        if weight.dim() != nd + 2 or x.shape[1] != weight.shape[1] * groups or len(set(weight.shape[2:])) != 1:
+            raise ValueError(f"fdconv: input {tuple(x.shape)} against a weight {tuple(weight.shape)} in {groups} groups")
+        x, weight = x.contiguous(), weight.contiguous()
+        lib = _lib.get_lib()
+        d = FdConvFn.desc(x, weight, groups, padding, grid_width)
+        y = torch.empty((x.shape[0], weight.shape[0], *x.shape[2:]), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            nbytes = lib.fdconv_forward_workspace_bytes(d)
+            ws = _ws(nbytes, x.device)
+            lib.fdconv_forward(d, x.data_ptr(), weight.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        ctx.d = d
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gy = gy.float().contiguous()
+        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_x or want_w):
+            return None, None, None, None, None
+        gx = torch.empty_like(x) if want_x else None
+        gw = torch.empty_like(weight) if want_w else None
+        with torch.cuda.device(gy.device):
+            nbytes = _lib.get_lib().fdconv_workspace_bytes(ctx.d)
+            ws = _ws(nbytes, gy.device)
+            _lib.get_lib().fdconv_backward(ctx.d, x.data_ptr(), weight.data_ptr(), gy.data_ptr(),
+                                           0 if gx is None else gx.data_ptr(), 0 if gw is None else gw.data_ptr(),
+                                           ws.data_ptr(), nbytes, stream=_stream())
+        return gx, gw, None, None, None
+
+
 class EngineRawOps:
     """The local stages of a spectral layer and their adjoints as plain calls (no autograd): what a hand-scheduled
     pipeline (mpu.ModeParallelSpectralConv: transform chunk j+1 while chunk j is on the wire) is built from.
