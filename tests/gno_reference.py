@@ -67,6 +67,47 @@ def transpose_csr(splits, index, cols):
     return col_splits, perm, row
 
 
+def lattice_points(rng, n, m, d, L):
+    """data (n, d) and queries (m, d) with coordinates k / L, k an integer in [0, L): for L a power of two differences,
+    squares and their sums are exact in fp32 and in float64, so is r^2 for r = j / L -- pairs at distance exactly r and
+    coincident pairs occur, and fp32 decides every one of them as float64 does (no band)."""
+    data = rng.integers(0, L, size=(n, d)) / L
+    queries = rng.integers(0, L, size=(m, d)) / L
+    return data.astype(np.float32), queries.astype(np.float32)
+
+
+def squared_distances(data, queries):
+    """float64 [m, n]; exact for lattice_points"""
+    data, queries = np.asarray(data, np.float64), np.asarray(queries, np.float64)
+    return ((queries[:, None, :] - data[None, :, :]) ** 2).sum(-1)
+
+
+def csr_reduce_torch(K, splits, F_=None, index=None, w=None, mean=False):
+    """csr_reduce as a torch formula autograd can differentiate (float64 in, float64 out): K (E, c) or (b, E, c), F_
+    None, (n, c) or (b, n, c); an empty row gives 0 under mean.  splits / index: int64 tensors."""
+    v = K
+    if F_ is not None:
+        v = v * F_[..., index, :]
+    if w is not None:
+        v = v * w.unsqueeze(-1)
+    rows = splits.numel() - 1
+    deg = splits[1:] - splits[:-1]
+    rep = torch.repeat_interleave(torch.arange(rows), deg)
+    out = torch.zeros(v.shape[:-2] + (rows, v.shape[-1]), dtype=v.dtype).index_add(-2, rep, v)
+    if mean:
+        out = out / deg.to(v.dtype).clamp(min=1).unsqueeze(-1)
+    return out
+
+
+def sinusoidal_embedding(x, num_frequencies, max_positions=10000):
+    """neuralop/layers/embeddings.py SinusoidalEmbedding, type "transformer", in the dtype of x (n, d) -> (n, 2 d nf):
+    [sin(x_i w_k), cos(x_i w_k)] with w_k = max_positions^(-2 k / nf), k fastest but for the sin / cos pair"""
+    k = torch.arange(num_frequencies, dtype=x.dtype)
+    freqs = (1.0 / max_positions) ** (k / num_frequencies * 2)
+    ang = x.unsqueeze(-1) * freqs
+    return torch.stack((ang.sin(), ang.cos()), dim=-1).reshape(x.shape[0], -1)
+
+
 def mlp_forward(weights, biases, x, act=F.gelu):
     for i, (W, b) in enumerate(zip(weights, biases)):
         x = F.linear(x, W, b)

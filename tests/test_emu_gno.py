@@ -91,10 +91,79 @@ def test_csr_transpose_of_any_csr(emu):
     assert g.transpose()[1] is g.transpose()[1]              # built once, kept
 
 
+def test_csr_transpose_across_the_scan_carry(emu):
+    """4100 columns: the column scan takes two passes (256 x 16 items each) and carries the first pass's total"""
+    rng = np.random.default_rng(6)
+    rows, cols = 40, 4100
+    splits, index = gr.random_csr(rng, rows, cols, rng.integers(0, 9, size=rows))
+    index[:70] = 4098                                        # a column past the carry, longer than one wave
+    index[70:80] = 4095
+    g = engine.CsrGraph(torch.from_numpy(splits), torch.from_numpy(index), cols)
+    for got, ref in zip(g.transpose(), gr.transpose_csr(splits, index, cols)):
+        np.testing.assert_array_equal(got.numpy(), ref)
+
+
+def _csr_with_bad_indices(rng, lengths, cols):
+    """a caller's CSR whose index holds -1, cols and a large value among valid entries: (splits, index, valid mask)"""
+    splits, index = gr.random_csr(rng, len(lengths), cols, np.array(lengths))
+    bad = rng.permutation(len(index))[:12]
+    index[bad[:4]], index[bad[4:8]], index[bad[8:]] = -1, cols, 1 << 40
+    valid = (index >= 0) & (index < cols)
+    assert valid.sum() == len(index) - 12
+    return splits, index, valid
+
+
+def test_out_of_range_indices_join_nothing(emu):
+    rng = np.random.default_rng(9)
+    cols, c, b = 11, 5, 2
+    splits, index, valid = _csr_with_bad_indices(rng, [0, 3, 70, 9, 1, 30], cols)
+    E, rows = len(index), len(splits) - 1
+    graph = engine.CsrGraph(torch.from_numpy(splits), torch.from_numpy(index), cols)
+    t = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32))       # noqa: E731
+    # reduce with F: such an edge contributes 0 (the mean still divides by the row's length)
+    K, Fv, w = t(b, E, c), t(b, cols, c), torch.from_numpy(rng.random(E).astype(np.float32))
+    Kz, safe = K.numpy() * valid[None, :, None], np.where(valid, index, 0)
+    for mean in (False, True):
+        out = engine._csr_reduce(graph, K, Fv, w, mean)
+        assert gr.rel_l2(out.numpy(), gr.csr_reduce(Kz, splits, Fv.numpy(), safe, w.numpy(), mean)) < 1e-6
+    g = t(b, rows, c)
+    gK = engine._csr_edge_grad(graph, g, Fv, w, False, True)
+    assert float(gK[:, torch.from_numpy(~valid)].abs().sum()) == 0.0 and float(gK.abs().sum()) > 0.0
+    # transpose: such an edge joins no column
+    col_splits, perm, row = (v.numpy() for v in graph.transpose())
+    ids = np.nonzero(valid)[0]
+    rcs, rperm, _ = gr.transpose_csr(splits, index[valid], cols)
+    np.testing.assert_array_equal(col_splits, rcs)
+    assert col_splits[-1] == valid.sum()
+    np.testing.assert_array_equal(perm[:len(ids)], ids[rperm])
+    assert np.all(perm[len(ids):] == -1)
+    np.testing.assert_array_equal(row, np.repeat(np.arange(rows), np.diff(splits)))
+    gF = engine._csr_reduce(graph, K, g, w, False, transposed=True)             # walks perm: the -1 tail is never read
+    v = Kz * g.numpy()[:, np.repeat(np.arange(rows), np.diff(splits))] * w.numpy()[None, :, None]
+    want = np.zeros((b, cols, c))
+    np.add.at(want, (slice(None), safe), v)
+    assert gr.rel_l2(gF.numpy(), want) < 1e-6
+    # first layer by point: H = 0 on such an edge, and no gradient through it
+    for gelu in (True, False):
+        Py, Px, bias = (v.requires_grad_(True) for v in (t(b, cols, c), t(rows, c), t(c)))
+        H = engine.EdgeLiftFn.apply(Py, Px, bias, graph, gelu)
+        assert float(H.detach()[:, torch.from_numpy(~valid)].abs().sum()) == 0.0
+        rep = np.repeat(np.arange(rows), np.diff(splits))
+        leaves = [v.detach().double().requires_grad_(True) for v in (Py, Px, bias)]
+        pre = leaves[0][:, safe] + leaves[1][rep] + leaves[2]
+        Href = (F.gelu(pre) if gelu else pre) * torch.from_numpy(valid)[None, :, None]
+        assert gr.rel_l2(H.detach().numpy(), Href.detach().numpy()) < 1e-6
+        gH = t(*H.shape)
+        H.backward(gH)
+        Href.backward(gH.double())
+        for mine, ref in zip((Py, Px, bias), leaves):
+            assert gr.rel_l2(mine.grad.numpy(), ref.grad.numpy()) < 1e-5
+
+
 LENGTHS = [0, 1, 65, 300, 7, 0, 2]                           # empty, single, past one wave, many passes of every group
 
 
-@pytest.mark.parametrize("c", [1, 3, 32, 33, 70])
+@pytest.mark.parametrize("c", [1, 3, 32, 33, 64, 70, 128])
 def test_reduce_and_edge_grad(emu, c):
     rng = np.random.default_rng(c)
     rows, n, b = len(LENGTHS), 11, 2
