@@ -482,6 +482,42 @@ int sc_fdconv_forward(const sc_fdconv_desc* desc, const float* x, const float* w
 int sc_fdconv_backward(const sc_fdconv_desc* desc, const float* x, const float* w, const float* gout, float* gx,
                        float* gw, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- equidistant discrete-continuous (DISCO) convolution of the local neural operator ----------------------------
+ * (neuralop/layers/discrete_continuous_convolution.py: EquidistantDiscreteContinuousConv2d and ...ConvTranspose2d)
+ *   kernel[o, c, i, j] = q_weight sum_k psi[k, i, j] weight[o, c, k]
+ *   transposed = 0:  y = conv2d(x, kernel, bias, stride (sh, sw), padding (pad_h, pad_w), groups), zero padding
+ *   transposed = 1:  y = conv_transpose2d(x, kernel, bias, stride, padding, output_padding (opad_h, opad_w), groups)
+ * x (batch, c_in, h_in, w_in), y (batch, c_out, h_out, w_out), psi (basis, ph, pw) -- the layer's filter buffer with its
+ * two spatial axes swapped and both flipped, contiguous --, bias (c_out) or null, all fp32 contiguous.  weight is
+ * (c_out, c_in / groups, basis) for transposed = 0 and (c_in, c_out / groups, basis) for transposed = 1.
+ * sc_disco_backward writes gx, gw, gbias or any subset (null = not wanted); gw is the weight-gradient correlation
+ * projected onto the basis, gbias the sum of gout over batch and points.  x may be null when gw is, weight when gx is.
+ * Workspaces as for sc_fdconv_*.  Refused before any launch: output extents that do not follow from the other fields
+ * (conv2d's / conv_transpose2d's own formula), groups that do not divide both channel counts, a support outside 1..15 or
+ * a stride outside 1..4 per axis, padding outside 0..support - 1, output padding outside 0..stride - 1 (0 for
+ * transposed = 0), a null required pointer, a small workspace, extents whose offsets leave the index types.
+ * sc_disco_path (0 = refused): SC_DISCO_PATH_MFMA for stride 1, support 3 x 3, padding 1, groups 1, c_in, c_out in
+ * {32, 64, 128} (the implicit GEMM of sc_fdconv on the exact-fp32 matrix instruction), the vector-ALU route otherwise.
+ * Deterministic: no float atomics, every sum in a fixed order that depends on the descriptor alone. */
+#define SC_DISCO_PATH_GENERAL 1
+#define SC_DISCO_PATH_MFMA 2
+typedef struct {
+  int64_t batch, c_in, c_out;
+  int64_t h_in, w_in, h_out, w_out;
+  int32_t groups, basis;
+  int32_t ph, pw, sh, sw, pad_h, pad_w, opad_h, opad_w;
+  int32_t transposed;
+  float q_weight;
+} sc_disco_desc;
+int sc_disco_path(const sc_disco_desc* desc);
+size_t sc_disco_workspace_bytes(const sc_disco_desc* desc);
+size_t sc_disco_forward_workspace_bytes(const sc_disco_desc* desc);
+int sc_disco_forward(const sc_disco_desc* desc, const float* x, const float* weight, const float* psi,
+                     const float* bias, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int sc_disco_backward(const sc_disco_desc* desc, const float* x, const float* weight, const float* psi,
+                      const float* gout, float* gx, float* gw, float* gbias, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -179,6 +179,16 @@ SC_FDCONV_PADDING = {"periodic": 0, "zeros": 1, "replicate": 2, "reflect": 3}
 SC_FDCONV_PATH_GENERAL, SC_FDCONV_PATH_MFMA = 1, 2
 
 
+class DiscoDesc(Structure):                                 # sc_disco_desc
+    _fields_ = [("batch", c_int64), ("c_in", c_int64), ("c_out", c_int64), ("h_in", c_int64), ("w_in", c_int64),
+                ("h_out", c_int64), ("w_out", c_int64), ("groups", c_int32), ("basis", c_int32), ("ph", c_int32),
+                ("pw", c_int32), ("sh", c_int32), ("sw", c_int32), ("pad_h", c_int32), ("pad_w", c_int32),
+                ("opad_h", c_int32), ("opad_w", c_int32), ("transposed", c_int32), ("q_weight", ctypes.c_float)]
+
+
+SC_DISCO_PATH_GENERAL, SC_DISCO_PATH_MFMA = 1, 2
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -242,7 +252,8 @@ class ScEngineLib:
                "sc_radius_fill", "sc_csr_transpose_workspace_bytes", "sc_csr_transpose", "sc_csr_reduce",
                "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd", "sc_fdconv_path", "sc_fdconv_workspace_bytes",
                "sc_fdconv_forward_workspace_bytes",
-               "sc_fdconv_forward", "sc_fdconv_backward"]
+               "sc_fdconv_forward", "sc_fdconv_backward", "sc_disco_path", "sc_disco_workspace_bytes",
+               "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -424,6 +435,16 @@ class ScEngineLib:
         L.sc_fdconv_forward.restype = c_int
         L.sc_fdconv_backward.argtypes = [POINTER(FdconvDesc)] + [c_void_p] * 6 + [c_size_t, c_void_p]
         L.sc_fdconv_backward.restype = c_int
+        L.sc_disco_path.argtypes = [POINTER(DiscoDesc)]
+        L.sc_disco_path.restype = c_int
+        L.sc_disco_workspace_bytes.argtypes = [POINTER(DiscoDesc)]
+        L.sc_disco_workspace_bytes.restype = c_size_t
+        L.sc_disco_forward_workspace_bytes.argtypes = [POINTER(DiscoDesc)]
+        L.sc_disco_forward_workspace_bytes.restype = c_size_t
+        L.sc_disco_forward.argtypes = [POINTER(DiscoDesc)] + [c_void_p] * 6 + [c_size_t, c_void_p]
+        L.sc_disco_forward.restype = c_int
+        L.sc_disco_backward.argtypes = [POINTER(DiscoDesc)] + [c_void_p] * 8 + [c_size_t, c_void_p]
+        L.sc_disco_backward.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -878,6 +899,40 @@ class ScEngineLib:
         """gx and / or gw of sc_fdconv_forward (a zero pointer: not wanted)"""
         self._check(self.lib.sc_fdconv_backward(byref(desc), x_ptr or None, w_ptr or None, gout_ptr or None,
                                                 gx_ptr or None, gw_ptr or None, ws_ptr or None, ws_bytes, stream))
+
+    @staticmethod
+    def disco_desc(*, batch, c_in, c_out, in_shape, out_shape, basis, support, stride=(1, 1), padding=(0, 0),
+                   output_padding=(0, 0), groups=1, q_weight=1.0, transposed=False):
+        d = DiscoDesc()
+        d.batch, d.c_in, d.c_out, d.groups, d.basis = int(batch), int(c_in), int(c_out), int(groups), int(basis)
+        (d.h_in, d.w_in), (d.h_out, d.w_out) = map(int, in_shape), map(int, out_shape)
+        (d.ph, d.pw), (d.sh, d.sw) = map(int, support), map(int, stride)
+        (d.pad_h, d.pad_w), (d.opad_h, d.opad_w) = map(int, padding), map(int, output_padding)
+        d.transposed, d.q_weight = int(transposed), float(q_weight)
+        return d
+
+    def disco_path(self, desc):
+        """the route of a descriptor: SC_DISCO_PATH_GENERAL, SC_DISCO_PATH_MFMA, or 0 where it is refused"""
+        return int(self.lib.sc_disco_path(byref(desc)))
+
+    def disco_workspace_bytes(self, desc):
+        return int(self.lib.sc_disco_workspace_bytes(byref(desc)))
+
+    def disco_forward_workspace_bytes(self, desc):
+        """what sc_disco_forward needs: the folded kernels alone"""
+        return int(self.lib.sc_disco_forward_workspace_bytes(byref(desc)))
+
+    def disco_forward(self, desc, x_ptr, w_ptr, psi_ptr, bias_ptr, y_ptr, ws_ptr, ws_bytes, stream=0):
+        """y = conv2d / conv_transpose2d(x, q sum_k psi[k] weight[.., k], bias) (sc_disco_forward)"""
+        self._check(self.lib.sc_disco_forward(byref(desc), x_ptr or None, w_ptr or None, psi_ptr or None,
+                                              bias_ptr or None, y_ptr or None, ws_ptr or None, ws_bytes, stream))
+
+    def disco_backward(self, desc, x_ptr, w_ptr, psi_ptr, gout_ptr, gx_ptr, gw_ptr, gbias_ptr, ws_ptr, ws_bytes,
+                       stream=0):
+        """gx, gw and / or gbias of sc_disco_forward (a zero pointer: not wanted)"""
+        self._check(self.lib.sc_disco_backward(byref(desc), x_ptr or None, w_ptr or None, psi_ptr or None,
+                                               gout_ptr or None, gx_ptr or None, gw_ptr or None, gbias_ptr or None,
+                                               ws_ptr or None, ws_bytes, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

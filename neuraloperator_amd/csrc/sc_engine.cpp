@@ -53,6 +53,7 @@
 #include "sc_host_modegemm.h"
 #include "sc_host_gno.h"
 #include "sc_host_fdconv.h"
+#include "sc_host_disco.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

@@ -224,9 +224,11 @@ SC_DEVICE void fdm_fetch(float (&xr)[FDM_CK], float (&wr)[9 * NOB], const float*
 // x (B, C_in, d1, d2), w the round-major folded copy [C_in / 8][9][8][C_out], y (B, C_out, d1, d2); NOB = C_out / 32.  Lane l of a wave supplies
 // A[o = l & 31][k = l >> 5] = W'[32 ob + o][c + k][t] and B[k][j = l & 31] = xpad[c + k][row + t1][col0 + j + t2], and
 // owns D[o = (v & 3) + 8 (v >> 2) + 4 (l >> 5)][j = l & 31] (sc_kernels_mfma.h).
-template <int NOB>
-SC_GLOBAL void SC_LAUNCH_BOUNDS(256)
-k_fdconv_mfma(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, const FdArgs a) {
+// BIAS: bias[o] (a null pointer: none) is added in the store -- the discrete-continuous convolution
+// (sc_kernels_disco.h) runs this body with its own folded weights; the finite-difference layer has no bias.
+template <int NOB, bool BIAS>
+SC_DEVICE void fdm_conv(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                        float* __restrict__ y, const FdArgs& a) {
   constexpr int CO = 32 * NOB;
   constexpr int WS = FDM_WS(CO);
   SC_SHARED float Lx[FDM_CK * FDM_XC];
@@ -306,10 +308,20 @@ k_fdconv_mfma(const float* __restrict__ x, const float* __restrict__ w, float* _
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         const int o = 32 * u + (v & 3) + 8 * (v >> 2) + 4 * lk;
-        y[((long long)bb * a.c_out + o) * plane + (long long)row * g.d2 + col] = acc[u][v];
+        float r = acc[u][v];
+        if (BIAS) {
+          if (bias) r += bias[o];
+        }
+        y[((long long)bb * a.c_out + o) * plane + (long long)row * g.d2 + col] = r;
       }
     }
   }
+}
+
+template <int NOB>
+SC_GLOBAL void SC_LAUNCH_BOUNDS(256)
+k_fdconv_mfma(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, const FdArgs a) {
+  fdm_conv<NOB, false>(x, w, nullptr, y, a);
 }
 
 // ------------------------------------------------------------------------------------------------- weight gradient

@@ -1567,6 +1567,75 @@ class FdConvFn(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
+class DiscoConvFn(torch.autograd.Function):
+    """The equidistant discrete-continuous convolution as one autograd node (sc_disco_forward / sc_disco_backward):
+    y = conv2d(x, kernel, bias, stride, padding, groups) or, transposed, conv_transpose2d(.., output_padding) with
+    kernel = q_weight sum_k psi[k] weight[.., k].  x (B, C_in, H, W), weight (.., .., K), psi (K, ph, pw) the layer's
+    get_local_filter_matrix(), bias (C_out) or None, all fp32.  Saves its inputs only."""
+
+    @staticmethod
+    def desc(x, weight, psi, groups, stride, padding, output_padding, q_weight, transposed):
+        c_in = int(x.shape[1])
+        c_out = int(weight.shape[1]) * int(groups) if transposed else int(weight.shape[0])
+        h, w, (ph, pw), (sh, sw) = int(x.shape[2]), int(x.shape[3]), psi.shape[1:], stride
+        if transposed:
+            out = ((h - 1) * sh - 2 * padding[0] + ph + output_padding[0],
+                   (w - 1) * sw - 2 * padding[1] + pw + output_padding[1])
+        else:
+            out = ((h + 2 * padding[0] - ph) // sh + 1, (w + 2 * padding[1] - pw) // sw + 1)
+        return _lib.ScEngineLib.disco_desc(batch=int(x.shape[0]), c_in=c_in, c_out=c_out, in_shape=(h, w),
+                                           out_shape=out, basis=int(psi.shape[0]), support=(int(ph), int(pw)),
+                                           stride=stride, padding=padding, output_padding=output_padding,
+                                           groups=groups, q_weight=q_weight, transposed=transposed)
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, psi, groups, stride, padding, output_padding, q_weight, transposed):
+        _require_gpu(x)
+        _require_gpu(weight, "weight")
+        tensors = [x, weight, psi] + ([] if bias is None else [bias])
+        if any(t.dtype != torch.float32 for t in tensors):
+            raise ValueError(f"disco: float32 tensors, got {[t.dtype for t in tensors]}")
+        lead = x.shape[1] if transposed else x.shape[1] // groups
+        if x.dim() != 4 or weight.dim() != 3 or psi.dim() != 3 or weight.shape[2] != psi.shape[0] or \
+                weight.shape[0 if transposed else 1] != lead:
+            raise ValueError(f"disco: input {tuple(x.shape)} against a weight {tuple(weight.shape)} in {groups} "
+                             f"groups and a filter basis {tuple(psi.shape)}")
+        x, weight, psi = x.contiguous(), weight.contiguous(), psi.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        lib = _lib.get_lib()
+        d = DiscoConvFn.desc(x, weight, psi, groups, stride, padding, output_padding, q_weight, transposed)
+        y = torch.empty((x.shape[0], d.c_out, max(d.h_out, 0), max(d.w_out, 0)), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            nbytes = lib.disco_forward_workspace_bytes(d)
+            ws = _ws(nbytes, x.device)
+            lib.disco_forward(d, x.data_ptr(), weight.data_ptr(), psi.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                              y.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        ctx.d, ctx.has_bias = d, bias is not None
+        ctx.save_for_backward(x, weight, psi)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, weight, psi = ctx.saved_tensors
+        gy = gy.float().contiguous()
+        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if not (want_x or want_w or want_b):
+            return (None,) * 10
+        gx = torch.empty_like(x) if want_x else None
+        gw = torch.empty_like(weight) if want_w else None
+        gb = torch.empty(ctx.d.c_out, dtype=torch.float32, device=gy.device) if want_b else None
+        lib = _lib.get_lib()
+        with torch.cuda.device(gy.device):
+            nbytes = lib.disco_workspace_bytes(ctx.d)
+            ws = _ws(nbytes, gy.device)
+            lib.disco_backward(ctx.d, x.data_ptr(), weight.data_ptr(), psi.data_ptr(), gy.data_ptr(),
+                               0 if gx is None else gx.data_ptr(), 0 if gw is None else gw.data_ptr(),
+                               0 if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        return (gx, gw, gb) + (None,) * 7
+
+
 class EngineRawOps:
     """The local stages of a spectral layer and their adjoints as plain calls (no autograd): what a hand-scheduled
     pipeline (mpu.ModeParallelSpectralConv: transform chunk j+1 while chunk j is on the wire) is built from.
