@@ -518,6 +518,49 @@ int sc_disco_backward(const sc_disco_desc* desc, const float* x, const float* we
                       const float* gout, float* gx, float* gw, float* gbias, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- discrete-continuous (DISCO) convolution on point clouds --------------------------------------------------------
+ * (neuralop/layers/discrete_continuous_convolution.py: DiscreteContinuousConv2d and DiscreteContinuousConvTranspose2d;
+ * the two differ only in how Psi is built)
+ *   Z[b, c, k, o]         = sum_i Psi[k, o, i] q[i] x[b, c, i]
+ *   out[b, g og + oc, o]  = sum_{c < cg, k} Z[b, g cg + c, k, o] weight[g og + oc, c, k] + bias[g og + oc]
+ * x (batch, c_in, n_in), out (batch, c_out, n_out), q (n_in), weight (c_out, c_in / groups, basis), bias (c_out) or null,
+ * all fp32 contiguous.  Psi comes as two CSR matrices with int32 splits and columns and fp32 values, nnz entries each:
+ *   forward CSR     rows = n_out basis, row o basis + k holds the input points i of (k, o, .) -- sc_dsparse_forward
+ *   transposed CSR  rows = n_in, row i holds the columns o basis + k of (k, o, i)             -- sc_dsparse_backward
+ * Entries are summed in stored order; a column outside its range counts as zero and is never used as an address.
+ * sc_dsparse_forward also writes z, (n_out, batch, basis, c_in) fp32: the engine's layout of Z, which
+ * sc_dsparse_backward reads for gw.  sc_dsparse_backward writes gx, gw, gbias or any subset (null = not wanted); psi_t,
+ * q and weight may be null when gx is, z when gw is.  The forward call needs sc_dsparse_forward_workspace_bytes(desc),
+ * the backward call sc_dsparse_workspace_bytes(desc).  Refused before any launch: groups that do not divide both
+ * channel counts, n_out basis, n_in or nnz beyond int32, a CSR whose rows or nnz differ from the descriptor's, a null
+ * required pointer, a small workspace.  Neither call reads device memory on the host or waits for the device.
+ * sc_dsparse_path (0 = refused): SC_DSPARSE_PATH_MFMA for groups = 1 and c_in, c_out in {32, 64, 128} (the two
+ * contractions and the weight gradient as tiled GEMMs on the exact-fp32 matrix instruction), SC_DSPARSE_PATH_GENERAL,
+ * the vector-ALU contraction, for every other descriptor.
+ * Deterministic: no float atomics, every sum in an order that depends on the descriptor and the CSR alone. */
+#define SC_DSPARSE_PATH_GENERAL 1
+#define SC_DSPARSE_PATH_MFMA 2
+typedef struct {
+  int64_t batch, c_in, c_out;
+  int64_t n_in, n_out, nnz;
+  int32_t groups, basis;
+} sc_dsparse_desc;
+typedef struct {
+  const int32_t* splits;   /* [rows + 1] */
+  const int32_t* cols;     /* [nnz] */
+  const float* vals;       /* [nnz] */
+  int64_t rows, nnz;
+} sc_dsparse_csr;
+int sc_dsparse_path(const sc_dsparse_desc* desc);
+size_t sc_dsparse_workspace_bytes(const sc_dsparse_desc* desc);
+size_t sc_dsparse_forward_workspace_bytes(const sc_dsparse_desc* desc);
+int sc_dsparse_forward(const sc_dsparse_desc* desc, const sc_dsparse_csr* psi, const float* x, const float* q,
+                       const float* weight, const float* bias, float* out, float* z, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int sc_dsparse_backward(const sc_dsparse_desc* desc, const sc_dsparse_csr* psi_t, const float* q, const float* weight,
+                        const float* z, const float* gout, float* gx, float* gw, float* gbias, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

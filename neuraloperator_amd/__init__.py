@@ -14,7 +14,8 @@ from .differentiation import FiniteDiff, FourierDiff  # noqa: F401
 from .losses import H1Loss, LpLoss  # noqa: F401
 from .gno import GNOBlock, IntegralTransform, NeighborSearch, segment_csr  # noqa: F401
 from .differential_conv import FiniteDifferenceConvolution  # noqa: F401
-from .discrete_continuous_convolution import (EquidistantDiscreteContinuousConv2d,  # noqa: F401
+from .discrete_continuous_convolution import (DiscreteContinuousConv2d, DiscreteContinuousConvTranspose2d,  # noqa: F401
+                                              EquidistantDiscreteContinuousConv2d,
                                               EquidistantDiscreteContinuousConvTranspose2d)
 from .local_no_block import LocalNOBlocks  # noqa: F401
 from .graph import GraphedStep, capture_step  # noqa: F401

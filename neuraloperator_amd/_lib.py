@@ -189,6 +189,18 @@ class DiscoDesc(Structure):                                 # sc_disco_desc
 SC_DISCO_PATH_GENERAL, SC_DISCO_PATH_MFMA = 1, 2
 
 
+class DsparseDesc(Structure):                               # sc_dsparse_desc
+    _fields_ = [("batch", c_int64), ("c_in", c_int64), ("c_out", c_int64), ("n_in", c_int64), ("n_out", c_int64),
+                ("nnz", c_int64), ("groups", c_int32), ("basis", c_int32)]
+
+
+class DsparseCsr(Structure):                                # sc_dsparse_csr
+    _fields_ = [("splits", c_void_p), ("cols", c_void_p), ("vals", c_void_p), ("rows", c_int64), ("nnz", c_int64)]
+
+
+SC_DSPARSE_PATH_GENERAL, SC_DSPARSE_PATH_MFMA = 1, 2
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -253,7 +265,9 @@ class ScEngineLib:
                "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd", "sc_fdconv_path", "sc_fdconv_workspace_bytes",
                "sc_fdconv_forward_workspace_bytes",
                "sc_fdconv_forward", "sc_fdconv_backward", "sc_disco_path", "sc_disco_workspace_bytes",
-               "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward"]
+               "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward", "sc_dsparse_path",
+               "sc_dsparse_workspace_bytes", "sc_dsparse_forward_workspace_bytes", "sc_dsparse_forward",
+               "sc_dsparse_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -445,6 +459,17 @@ class ScEngineLib:
         L.sc_disco_forward.restype = c_int
         L.sc_disco_backward.argtypes = [POINTER(DiscoDesc)] + [c_void_p] * 8 + [c_size_t, c_void_p]
         L.sc_disco_backward.restype = c_int
+        L.sc_dsparse_path.argtypes = [POINTER(DsparseDesc)]
+        L.sc_dsparse_path.restype = c_int
+        L.sc_dsparse_workspace_bytes.argtypes = [POINTER(DsparseDesc)]
+        L.sc_dsparse_workspace_bytes.restype = c_size_t
+        L.sc_dsparse_forward_workspace_bytes.argtypes = [POINTER(DsparseDesc)]
+        L.sc_dsparse_forward_workspace_bytes.restype = c_size_t
+        L.sc_dsparse_forward.argtypes = [POINTER(DsparseDesc), POINTER(DsparseCsr)] + [c_void_p] * 7 + [c_size_t, c_void_p]
+        L.sc_dsparse_forward.restype = c_int
+        L.sc_dsparse_backward.argtypes = [POINTER(DsparseDesc), POINTER(DsparseCsr)] + [c_void_p] * 8 + \
+            [c_size_t, c_void_p]
+        L.sc_dsparse_backward.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -933,6 +958,41 @@ class ScEngineLib:
         self._check(self.lib.sc_disco_backward(byref(desc), x_ptr or None, w_ptr or None, psi_ptr or None,
                                                gout_ptr or None, gx_ptr or None, gw_ptr or None, gbias_ptr or None,
                                                ws_ptr or None, ws_bytes, stream))
+
+    @staticmethod
+    def dsparse_desc(*, batch, c_in, c_out, n_in, n_out, nnz, basis, groups=1):
+        d = DsparseDesc()
+        d.batch, d.c_in, d.c_out, d.n_in, d.n_out, d.nnz = int(batch), int(c_in), int(c_out), int(n_in), int(n_out), int(nnz)
+        d.groups, d.basis = int(groups), int(basis)
+        return d
+
+    @staticmethod
+    def dsparse_csr(splits_ptr, cols_ptr, vals_ptr, rows, nnz):
+        """a CSR form of Psi for sc_dsparse_*: int32 splits (rows + 1) and columns, fp32 values, as raw pointers"""
+        return DsparseCsr(splits_ptr or None, cols_ptr or None, vals_ptr or None, int(rows), int(nnz))
+
+    def dsparse_path(self, desc):
+        """the route of a descriptor: SC_DSPARSE_PATH_GENERAL, SC_DSPARSE_PATH_MFMA, or 0 where it is refused"""
+        return int(self.lib.sc_dsparse_path(byref(desc)))
+
+    def dsparse_workspace_bytes(self, desc):
+        return int(self.lib.sc_dsparse_workspace_bytes(byref(desc)))
+
+    def dsparse_forward_workspace_bytes(self, desc):
+        return int(self.lib.sc_dsparse_forward_workspace_bytes(byref(desc)))
+
+    def dsparse_forward(self, desc, csr, x_ptr, q_ptr, w_ptr, bias_ptr, out_ptr, z_ptr, ws_ptr, ws_bytes, stream=0):
+        """out = contraction of Z = Psi (q x) with the weight, + bias; Z (n_out, batch, basis, c_in) is written too"""
+        self._check(self.lib.sc_dsparse_forward(byref(desc), byref(csr), x_ptr or None, q_ptr or None, w_ptr or None,
+                                                bias_ptr or None, out_ptr or None, z_ptr or None, ws_ptr or None,
+                                                ws_bytes, stream))
+
+    def dsparse_backward(self, desc, csr_t, q_ptr, w_ptr, z_ptr, gout_ptr, gx_ptr, gw_ptr, gbias_ptr, ws_ptr, ws_bytes,
+                         stream=0):
+        """gx, gw and / or gbias of sc_dsparse_forward (a zero pointer: not wanted)"""
+        self._check(self.lib.sc_dsparse_backward(byref(desc), byref(csr_t) if csr_t is not None else None, q_ptr or None,
+                                                 w_ptr or None, z_ptr or None, gout_ptr or None, gx_ptr or None,
+                                                 gw_ptr or None, gbias_ptr or None, ws_ptr or None, ws_bytes, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

@@ -54,6 +54,7 @@
 #include "sc_host_gno.h"
 #include "sc_host_fdconv.h"
 #include "sc_host_disco.h"
+#include "sc_host_disco_sparse.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

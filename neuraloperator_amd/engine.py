@@ -1636,6 +1636,80 @@ class DiscoConvFn(torch.autograd.Function):
         return (gx, gw, gb) + (None,) * 7
 
 
+class SparseDiscoFn(torch.autograd.Function):
+    """The discrete-continuous convolution on point clouds as one autograd node (sc_dsparse_forward /
+    sc_dsparse_backward): out[b, o, :] = sum_{c, k} weight[o, c, k] (Psi[k] (q x[b, c])) + bias.  x (B, C_in, n_in), weight
+    (C_out, C_in / groups, K), bias (C_out) or None, q (n_in), all fp32; csr and csr_t are the layer's (splits, cols, vals)
+    triples of Psi by (output point, basis) rows and by input-point rows (int32, int32, fp32).  Saves Z = Psi (q x) in the
+    engine's layout (n_out, B, K, C_in) for the weight gradient, as the reference's autograd saves its own.  Neither pass
+    waits for the device."""
+
+    @staticmethod
+    def desc(x, weight, n_out, nnz, groups):
+        return _lib.ScEngineLib.dsparse_desc(batch=int(x.shape[0]), c_in=int(x.shape[1]), c_out=int(weight.shape[0]),
+                                             n_in=int(x.shape[2]), n_out=int(n_out), nnz=int(nnz),
+                                             basis=int(weight.shape[2]), groups=int(groups))
+
+    @staticmethod
+    def _csr(triple, rows):
+        splits, cols, vals = triple
+        if splits.dtype != torch.int32 or cols.dtype != torch.int32 or vals.dtype != torch.float32:
+            raise ValueError("dsparse: a CSR is int32 splits, int32 columns and float32 values")
+        if splits.numel() != rows + 1 or cols.numel() != vals.numel():
+            raise ValueError(f"dsparse: a CSR of {rows} rows has {rows + 1} splits and as many columns as values")
+        return _lib.ScEngineLib.dsparse_csr(splits.data_ptr(), cols.data_ptr(), vals.data_ptr(), rows, vals.numel())
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, q, n_out, groups, csr, csr_t):
+        _require_gpu(x)
+        _require_gpu(weight, "weight")
+        tensors = [x, weight, q] + ([] if bias is None else [bias])
+        if any(t.dtype != torch.float32 for t in tensors):
+            raise ValueError(f"dsparse: float32 tensors, got {[t.dtype for t in tensors]}")
+        if x.dim() != 3 or weight.dim() != 3 or x.shape[1] != weight.shape[1] * groups or q.numel() != x.shape[2]:
+            raise ValueError(f"dsparse: input {tuple(x.shape)} against a weight {tuple(weight.shape)} in {groups} groups "
+                             f"and {q.numel()} quadrature weights")
+        x, weight, q = x.contiguous(), weight.contiguous(), q.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        csr, csr_t = tuple(t.contiguous() for t in csr), tuple(t.contiguous() for t in csr_t)
+        lib = _lib.get_lib()
+        d = SparseDiscoFn.desc(x, weight, n_out, csr[2].numel(), groups)
+        m = SparseDiscoFn._csr(csr, d.n_out * d.basis)
+        out = torch.empty((d.batch, d.c_out, d.n_out), dtype=torch.float32, device=x.device)
+        z = torch.empty((d.n_out, d.batch, d.basis, d.c_in), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            nbytes = lib.dsparse_forward_workspace_bytes(d)
+            ws = _ws(nbytes, x.device)
+            lib.dsparse_forward(d, m, x.data_ptr(), q.data_ptr(), weight.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                                out.data_ptr(), z.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        ctx.d, ctx.has_bias = d, bias is not None
+        ctx.save_for_backward(weight, q, z, *csr_t)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        weight, q, z, *csr_t = ctx.saved_tensors
+        gy = gy.float().contiguous()
+        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if not (want_x or want_w or want_b):
+            return (None,) * 8
+        d = ctx.d
+        gx = torch.empty((d.batch, d.c_in, d.n_in), dtype=torch.float32, device=gy.device) if want_x else None
+        gw = torch.empty_like(weight) if want_w else None
+        gb = torch.empty(d.c_out, dtype=torch.float32, device=gy.device) if want_b else None
+        lib = _lib.get_lib()
+        mt = SparseDiscoFn._csr(csr_t, d.n_in)
+        with torch.cuda.device(gy.device):
+            nbytes = lib.dsparse_workspace_bytes(d)
+            ws = _ws(nbytes, gy.device)
+            lib.dsparse_backward(d, mt, q.data_ptr(), weight.data_ptr(), z.data_ptr(), gy.data_ptr(),
+                                 0 if gx is None else gx.data_ptr(), 0 if gw is None else gw.data_ptr(),
+                                 0 if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        return (gx, gw, gb) + (None,) * 5
+
+
 class EngineRawOps:
     """The local stages of a spectral layer and their adjoints as plain calls (no autograd): what a hand-scheduled
     pipeline (mpu.ModeParallelSpectralConv: transform chunk j+1 while chunk j is on the wire) is built from.
