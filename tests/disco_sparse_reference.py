@@ -7,7 +7,8 @@ import os
 import numpy as np
 import torch
 
-from disco_reference import GOLDEN, fp32_randn, load_reference_module, reference_available, rel_l2  # noqa: F401
+from disco_reference import (GOLDEN, fp32_randn, gamma, load_reference_module, reference_available, rel_l2,  # noqa: F401
+                             worst_ratio)
 
 GENERAL, MFMA = 1, 2
 
@@ -169,6 +170,79 @@ DESC_CASES = {
     "mfma_rows_257_two_slices_129_past_a_tile": desc_case(c_in=32, c_out=32, n_out=257, batch=1, n_in=4, basis=1,
                                                           route=MFMA),
 }
+
+
+# Kernel-edge cases: the round, tile, slice and route edges of sc_kernels_disco_sparse.h, run on the device by
+# tests/test_gpu_disco_sparse_kernels.py; EMU_KERNEL_CASES names those the one-thread-per-lane emulation finishes in
+# seconds.  Groups are lettered as in that file's docstring.
+def _kernel_cases():
+    small = dict(n_in=6, n_out=5, basis=2, batch=1)
+    c = {                                                    # a: the 128-column rounds of k_dsp_contract
+        "a_forward_group_straddles_column_128": desc_case(c_in=192, c_out=6, groups=2, **small),
+        "a_forward_cg130_three_rounds": desc_case(c_in=260, c_out=4, groups=2, **small),
+        "a_data_gradient_c_out_130": desc_case(c_in=3, c_out=130, **small),
+        "a_data_gradient_og96_straddles": desc_case(c_in=4, c_out=192, groups=2, **small),
+        "a_depthwise130": desc_case(c_in=130, c_out=130, groups=130, **small),
+    }
+    for og in (15, 16, 17):                                  # b: the tiles of k_dsp_wgrad
+        c[f"b_og{og}"] = desc_case(c_in=3, c_out=og, **small)
+    for K, cg in ((3, 21), (2, 32), (5, 13)):
+        c[f"b_K_cg_{K * cg}"] = desc_case(c_in=cg, c_out=5, n_in=6, n_out=5, basis=K, batch=1)
+    for rows in (31, 32, 33):
+        c[f"b_rows{rows}"] = desc_case(c_in=2, c_out=2, n_in=5, n_out=rows, basis=2, batch=1)
+    # c: the cap of 64 slices (rows = 64 * 252 + 2 and beyond); 0 to 4 entries to a row of Psi
+    c["c_slice_cap_rows_16130"] = desc_case(c_in=2, c_out=2, n_in=4, n_out=16130, basis=1, batch=1, density=0.5)
+    c["c_slice_cap_mfma_rows_16400_per_slice_257"] = desc_case(c_in=32, c_out=32, n_in=4, n_out=16400, basis=1, batch=1,
+                                                               density=0.5, route=MFMA)
+    for i, ci in enumerate((32, 64, 128)):                   # d: matrix cores; 129 rows: one slice, a ragged last trip
+        for j, co in enumerate((32, 64, 128)):
+            c[f"d_mfma_{ci}_{co}_rows129"] = desc_case(c_in=ci, c_out=co, n_in=5, n_out=129, basis=(1, 3)[(i + j) % 2],
+                                                       batch=1, route=MFMA)
+    c["d_mfma_32_32_rows127_basis3"] = desc_case(c_in=32, c_out=32, n_in=5, n_out=127, basis=3, batch=1, route=MFMA)
+    c["d_mfma_32_32_rows128_basis1"] = desc_case(c_in=32, c_out=32, n_in=5, n_out=128, basis=1, batch=1, route=MFMA)
+    c["d_mfma_32_32_rows129_basis3"] = desc_case(c_in=32, c_out=32, n_in=5, n_out=43, basis=3, batch=3, route=MFMA)
+    return c
+
+
+KERNEL_DESC_CASES = _kernel_cases()
+EMU_KERNEL_CASES = tuple(k for k in KERNEL_DESC_CASES if k[0] in "ab")
+DESC_CASES.update({k: KERNEL_DESC_CASES[k] for k in EMU_KERNEL_CASES})   # the emulation tier runs DESC_CASES
+
+
+def wgrad_slices(cfg):
+    """(slices, per_slice) of the weight gradient as dsp_plan (sc_host_disco_sparse.h) cuts its rows"""
+    rows = cfg["n_out"] * cfg["batch"]
+    s = min(max(-(-rows // 256), 1), 64)
+    per = -(-rows // s)
+    return -(-rows // per), per
+
+
+def roundings(cfg, keep=None):
+    """N of (out, gx, gw, gbias): the fp32 roundings on the longest path to one element, counted in
+    sc_kernels_disco_sparse.h.  An entry of Z carries z = 1 + row: the product q x (k_dsp_pack) and one fmaf per entry
+    of a row of Psi (k_dsp_spmm); row = the longest row of the pattern `keep` (K, n_out, n_in), n_in without one, and
+    col = its longest column over (k, o), K n_out without one.
+      out    z + one fmaf per (basis function, input channel of the group) + the bias     k_dsp_contract / gemm, unpack
+      gx     one fmaf per output channel of the group + one per entry of a column of Psi (col) + the
+             product with q                                                              k_dsp_contract, spmm, unpack
+      gw     z + one fmaf per row of a slice + the slices                                k_dsp_wgrad(_mfma), wreduce
+      gbias  one addition per row of a slice (+ 1: the two halves of a wave on the matrix cores) + the slices
+    Any order of summation stays below these, so they hold for both routes."""
+    slices, per = wgrad_slices(cfg)
+    row = cfg["n_in"] if keep is None else int(keep.sum(dim=2).max())
+    col = cfg["basis"] * cfg["n_out"] if keep is None else int(keep.sum(dim=(0, 1)).max())
+    z = 1 + row
+    return (z + cfg["basis"] * (cfg["c_in"] // cfg["groups"]) + 1,
+            cfg["c_out"] // cfg["groups"] + col + 1,
+            z + per + slices,
+            per + 1 + slices)
+
+
+def abs_bounds(cfg, psi, keep, x, w, q, b, g):
+    """((A_out, A_gx, A_gw, A_gbias), (N ..)): A is the layer and its gradients in float64 on |x|, |w|, |Psi|, |q|,
+    |bias| with cotangent |g|"""
+    ab = None if b is None else b.abs()
+    return sparse_disco_with_grads(x.abs(), w.abs(), ab, psi.double().abs(), q.abs(), g.abs(), cfg["groups"]), roundings(cfg, keep)
 
 
 def desc_psi(cfg, gen):

@@ -121,6 +121,55 @@ LIVE_CASES = {
 }
 
 
+# Kernel-edge cases: free-standing descriptors at the tile, chunk and route edges of sc_kernels_fdconv.h, run on the
+# device by tests/test_gpu_fdconv_kernels.py (the float64 helper is the reference); EMU_KERNEL_CASES names those the
+# one-thread-per-lane emulation finishes in a few seconds.  Groups are lettered as in that file's docstring.
+def _kernel_cases():
+    modes = ("periodic", "zeros", "replicate", "reflect")
+    c = {}
+    for k in (3, 5, 7):                                      # a: one past FD_TR and FD_TC (and FD_OCB), every mode
+        for m in modes:
+            c[f"a_17x65_k{k}_{m}"] = _case((17, 65), 2, 5, k=k, padding=m)
+    for m in ("replicate", "reflect"):                       # a point and its high pad in different tiles on both axes
+        c[f"a_33x130_k7_{m}"] = _case((33, 130), 2, 5, k=7, padding=m, batch=1)
+    for m in ("replicate", "reflect"):                       # b: d + 2 r crosses a tile, d does not
+        c[f"b_11x59_k7_{m}"] = _case((11, 59), 2, 3, k=7, padding=m)
+        c[f"b_16x64_k3_{m}"] = _case((16, 64), 2, 3, k=3, padding=m)
+    c["c_reflect_k7_4x4"] = _case((4, 4), 2, 3, k=7, padding="reflect")          # c: smallest legal extents
+    c["c_reflect_k5_3"] = _case((3,), 2, 3, k=5, padding="reflect")
+    c["c_periodic_k7_3x3"] = _case((3, 3), 2, 3, k=7)
+    c["c_periodic_k5_2x70"] = _case((2, 70), 2, 3, k=5)
+    c["c_periodic_k3_1x65"] = _case((1, 65), 2, 3, k=3)
+    for m in modes:                                          # d: three axes
+        c[f"d_3x17x65_k3_{m}"] = _case((3, 17, 65), 2, 3, k=3, padding=m)
+    c["d_2x5x6_k5_zeros"] = _case((2, 5, 6), 2, 3, k=5, padding="zeros")
+    c["d_2x5x6_k5_replicate"] = _case((2, 5, 6), 2, 3, k=5, padding="replicate")
+    c["d_7x4x4_k7_reflect"] = _case((7, 4, 4), 2, 3, k=7, padding="reflect")     # reflect needs extents above k / 2 = 3
+    for og in (3, 4, 5):                                     # e: output channels of a group around FD_OCB
+        c[f"e_cout_g{og}_groups1"] = _case((5, 9), 2, og)
+        c[f"e_cout_g{og}_groups2"] = _case((5, 9), 4, 2 * og, groups=2, padding="reflect")
+    c["e_depthwise5"] = _case((5, 9), 5, 5, groups=5, padding="zeros")
+    c["f_one_chunk_33_31"] = _case((17, 65), 33, 31, batch=1)                    # f: 1023 jobs, 1024 / jobs = 1 chunk
+    c["f_one_chunk_33_32"] = _case((17, 65), 33, 32, batch=1)                    # 1056 jobs >= 1024: the other branch
+    c["f_704_batch3_empty_chunks"] = _case((704,), 2, 2, batch=3)                # 33 units, 32 chunks of 2: 17.. are empty
+    c["f_704_batch1"] = _case((704,), 2, 2, batch=1)                             # 11 units, 11 chunks
+    for ci in (32, 64, 128):                                 # g: matrix cores, one past FDM_TR and FDM_TC
+        for co in (32, 64, 128):
+            for m in ("periodic", "zeros"):
+                c[f"g_mfma_{ci}_{co}_{m}"] = _case((5, 33), ci, co, padding=m, batch=1, route=MFMA)
+    c["g_mfma_32_32_1x31"] = _case((1, 31), 32, 32, padding="zeros", batch=1, route=MFMA)
+    c["g_mfma_32_32_4x32"] = _case((4, 32), 32, 32, padding="zeros", batch=1, route=MFMA)
+    c["g_mfma_32_32_periodic_2x2"] = _case((2, 2), 32, 32, batch=1, route=MFMA)
+    c["g_mfma_32_32_49x129_65_units"] = _case((49, 129), 32, 32, batch=1, route=MFMA)   # 64 chunks of 2, 33 carry data
+    return c
+
+
+KERNEL_CASES = _kernel_cases()
+EMU_KERNEL_CASES = ("b_16x64_k3_replicate", "b_16x64_k3_reflect", "c_reflect_k7_4x4", "c_reflect_k5_3",
+                    "c_periodic_k7_3x3", "c_periodic_k5_2x70", "c_periodic_k3_1x65", "d_2x5x6_k5_zeros",
+                    "d_2x5x6_k5_replicate")
+
+
 def grid_width_of(cfg):
     return 1.0 / cfg["dims"][-1]
 
@@ -195,6 +244,106 @@ def record_bars(cfg, rec):
     if cfg["smooth"]:
         return tuple(2.0 * float(rec["f32err:" + k]) for k in ("out", "grad:x", "grad:weight"))
     return (1e-5, 1e-5, 1e-5)
+
+
+# ---- free-standing descriptors through the C-ABI (the emulation and the GPU tier run the same runner) ------------------
+def desc_of(cfg, h):
+    from neuraloperator_amd import _lib
+    return _lib.ScEngineLib.fdconv_desc(dims=cfg["dims"], batch=cfg["batch"], c_in=cfg["c_in"], c_out=cfg["c_out"],
+                                        k=cfg["k"], groups=cfg["groups"], padding=cfg["padding"], inv_h=1.0 / h)
+
+
+def run_descriptor(lib, cfg, x, w, g, h, want_x=True, want_w=True, device="cpu", stream=0):
+    """sc_fdconv_forward + sc_fdconv_backward on tensors moved to `device`: (out, gx, gw) on the host"""
+    x, w, g = (t.to(device) for t in (x, w, g))
+    d = desc_of(cfg, h)
+    nbytes, fbytes = lib.fdconv_workspace_bytes(d), lib.fdconv_forward_workspace_bytes(d)
+    assert 0 < fbytes <= nbytes
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    y = torch.full((cfg["batch"], cfg["c_out"], *cfg["dims"]), float("nan"), device=device)
+    lib.fdconv_forward(d, x.data_ptr(), w.data_ptr(), y.data_ptr(), ws.data_ptr(), fbytes, stream)  # its own, smaller size
+    gx = torch.full_like(x, float("nan")) if want_x else None
+    gw = torch.full_like(w, float("nan")) if want_w else None
+    ws.fill_(0xff)                                           # the backward call owes nothing to the forward call's workspace
+    lib.fdconv_backward(d, x.data_ptr(), w.data_ptr(), g.data_ptr(), 0 if gx is None else gx.data_ptr(),
+                        0 if gw is None else gw.data_ptr(), ws.data_ptr(), nbytes, stream)
+    return tuple(None if t is None else t.cpu() for t in (y, gx, gw))
+
+
+# ---- per-element bound: |got - want| <= gamma_N A ----------------------------------------------------------------------
+U = 2.0 ** -24                                               # unit round-off of fp32
+
+
+def gamma(n):
+    return n * U / (1.0 - n * U)
+
+
+def wgrad_plan(cfg):
+    """(units, chunks, per_chunk, parts) of the weight gradient as fd_plan (sc_host_fdconv.h) cuts it"""
+    dense = cfg["route"] == MFMA
+    d = (1,) * (3 - len(cfg["dims"])) + tuple(cfg["dims"])
+    tr, tc = (FDM_TR, FDM_TC) if dense else (FD_TR, FD_TC)
+    units = cfg["batch"] * (1 if dense else d[0]) * (-(-d[1] // tr)) * (-(-d[2] // tc))
+    jobs = cfg["c_out"] * (cfg["c_in"] // cfg["groups"]) * (cfg["k"] if len(cfg["dims"]) == 3 else 1)
+    want = 64 if dense else (1 if jobs >= 1024 else min(1024 // jobs, 32))
+    chunks = min(units, want)
+    return units, chunks, -(-units // chunks), 4 * chunks if dense else chunks
+
+
+def roundings(cfg):
+    """N of (out, gx, gw): the fp32 roundings on the longest path to one element, counted in sc_kernels_fdconv.h.
+    A folded weight carries fold = taps + 1 of them: taps - 1 additions of the centre tap's sum (k_fdconv_fold), its
+    product with 1 / h, and the rounding of 1 / h to fp32 by the caller.
+      out   fold + one fmaf per (input channel of the group, tap)                                     k_fdconv, fdm_conv
+      gx    fold + one fmaf per (output channel of the group, tap); replicate / reflect add the pre-image sum of
+            k_fdconv_unpad, (r + 1)^nd terms at a corner at the most
+      gw    one fmaf per (batch entry, point) + the 8 levels of fd_block_sum (general route; the matrix-core route adds
+            its four waves in the partial sum instead) + the partial sums of k_fdconv_wreduce + the subtraction, the
+            product with 1 / h and the rounding of 1 / h
+    Any order of summation stays below these, so they hold for both routes."""
+    nd, r = len(cfg["dims"]), cfg["k"] // 2
+    taps = cfg["k"] ** nd
+    fold = taps + 1
+    pts = int(np.prod(cfg["dims"]))
+    unpad = (r + 1) ** nd if cfg["padding"] in ("replicate", "reflect") else 0
+    return (fold + (cfg["c_in"] // cfg["groups"]) * taps,
+            fold + (cfg["c_out"] // cfg["groups"]) * taps + unpad,
+            cfg["batch"] * pts + 8 + wgrad_plan(cfg)[3] + 3)
+
+
+def abs_bounds(cfg, x, w, g, grid_width):
+    """((A_out, A_gx, A_gw), (N_out, N_gx, N_gw)): A is the layer on absolute values in float64 -- |x| and |g| with a
+    kernel whose off-centre taps are |W| / |h| and whose centre tap is sum |W_offcentre| / |h| (the size of the terms of
+    the cancelling fold as well); A_gw[t] = (A_G[t] + A_G[centre]) / |h| with A_G = sum |g| |xpad|, 0 at the centre."""
+    nd, r, groups = len(cfg["dims"]), cfg["k"] // 2, cfg["groups"]
+    conv = getattr(F, f"conv{nd}d")
+    ah = abs(float(grid_width))
+    x64 = x.detach().double().cpu().abs().requires_grad_(True)
+    flat = w.detach().double().cpu().abs().reshape(*w.shape[:2], -1) / ah
+    c = flat.shape[-1] // 2
+    flat[..., c] = 0.0
+    flat[..., c] = flat.sum(-1)
+    ones = torch.ones_like(w, dtype=torch.float64).requires_grad_(True)   # d / d ones of sum |g| conv(|xpad|, ones) = A_G
+    xp = F.pad(x64, [r, r] * nd, mode=PAD_MODE[cfg["padding"]])
+    g64 = g.detach().double().cpu().abs()
+    out = conv(xp, flat.reshape(w.shape), groups=groups)
+    out.backward(g64, retain_graph=True)
+    a_gx = x64.grad.clone()
+    (a_g,) = torch.autograd.grad(conv(xp.detach(), ones, groups=groups), ones, g64)
+    a_g = a_g.reshape(*w.shape[:2], -1)
+    a_gw = (a_g + a_g[..., c:c + 1]) / ah
+    a_gw[..., c] = 0.0
+    return (out.detach().numpy(), a_gx.numpy(), a_gw.reshape(w.shape).numpy()), roundings(cfg)
+
+
+def worst_ratio(got, want, bound, n):
+    """max |got - want| / (gamma_n bound) over the elements; where bound == 0 the value must be exactly 0 (inf if not)"""
+    got, want, bound = (np.asarray(t, np.float64) for t in (got, want, bound))
+    err, lim = np.abs(got - want), gamma(n) * bound
+    zero = bound == 0
+    if (zero & (got != 0)).any() or not np.isfinite(got).all():
+        return float("inf")
+    return float((err[~zero] / lim[~zero]).max()) if (~zero).any() else 0.0
 
 
 # ---- the verbatim reference, where it exists --------------------------------------------------------------------------

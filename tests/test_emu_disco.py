@@ -19,90 +19,9 @@ def emu():
         yield lib
 
 
-def _cfg(in_shape, support, c_in=3, c_out=5, stride=(1, 1), padding=None, opad=(0, 0), groups=1, basis=4, batch=2,
-         transposed=False, bias=True, route=dr.GENERAL):
-    padding = tuple((p + 1) // 2 - 1 for p in support) if padding is None else padding
-    return dict(in_shape=in_shape, support=support, c_in=c_in, c_out=c_out, stride=stride, padding=padding, opad=opad,
-                groups=groups, basis=basis, batch=batch, transposed=transposed, bias=bias, route=route)
-
-
-CASES = {
-    "3x3_one_past_a_tile_column": _cfg((5, 65), (3, 3)),
-    "3x3_one_past_a_tile_row": _cfg((17, 6), (3, 3), batch=1),
-    "5x5_stride2": _cfg((18, 21), (5, 5), stride=(2, 2)),
-    "7x5_strides_3x4_pad_small": _cfg((20, 23), (7, 5), stride=(3, 4), padding=(1, 0), batch=1),
-    "4x3_even_rectangular": _cfg((9, 10), (4, 3)),
-    "2x2_pad0": _cfg((7, 7), (2, 2)),
-    "15x15_cap": _cfg((17, 16), (15, 15), c_in=2, c_out=2, batch=1),
-    "1x1": _cfg((4, 5), (1, 1)),
-    "groups2_odd_channels": _cfg((6, 7), (3, 3), c_in=6, c_out=10, groups=2),
-    "depthwise_one_row": _cfg((1, 9), (3, 3), c_in=5, c_out=5, groups=5),
-    "no_bias_stride4": _cfg((16, 12), (5, 9), stride=(4, 4), bias=False, batch=1),
-    "transpose_stride2": _cfg((5, 6), (5, 5), stride=(2, 2), opad=(1, 1), transposed=True),
-    "transpose_strides_2x3_grouped": _cfg((4, 5), (7, 5), c_in=4, c_out=6, stride=(2, 3), opad=(1, 0), groups=2,
-                                          transposed=True),
-    "transpose_stride1_even": _cfg((6, 6), (4, 4), padding=(2, 2), transposed=True, batch=1),
-    "transpose_past_a_tile": _cfg((9, 33), (3, 3), stride=(2, 2), opad=(1, 1), c_in=2, c_out=3, batch=1,
-                                  transposed=True),
-    "mfma_32_32": _cfg((5, 34), (3, 3), c_in=32, c_out=32, batch=1, route=dr.MFMA),
-    "mfma_64_32_no_bias": _cfg((4, 8), (3, 3), c_in=64, c_out=32, batch=1, bias=False, route=dr.MFMA),
-    "mfma_32_64_transposed": _cfg((4, 8), (3, 3), c_in=32, c_out=64, batch=2, transposed=True, route=dr.MFMA),
-}
-
-
-def _weight_shape(cfg):
-    if cfg["transposed"]:
-        return (cfg["c_in"], cfg["c_out"] // cfg["groups"], cfg["basis"])
-    return (cfg["c_out"], cfg["c_in"] // cfg["groups"], cfg["basis"])
-
-
-def _inputs(cfg, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = dr.fp32_randn((cfg["batch"], cfg["c_in"], *cfg["in_shape"]), g)
-    w = dr.fp32_randn(_weight_shape(cfg), g) * 0.3
-    psi = dr.fp32_randn((cfg["basis"], *cfg["support"]), g)
-    b = dr.fp32_randn((cfg["c_out"],), g) if cfg["bias"] else None
-    shape = dr.out_shape_of(x.shape, cfg["c_out"], psi.shape, cfg["stride"], cfg["padding"], cfg["opad"],
-                            cfg["transposed"])
-    return x, w, psi, b, dr.fp32_randn(shape, g)
-
-
-Q = 0.0625
-
-
-def _desc(cfg, out_shape, **over):
-    kw = dict(batch=cfg["batch"], c_in=cfg["c_in"], c_out=cfg["c_out"], in_shape=cfg["in_shape"], out_shape=out_shape,
-              basis=cfg["basis"], support=cfg["support"], stride=cfg["stride"], padding=cfg["padding"],
-              output_padding=cfg["opad"], groups=cfg["groups"], q_weight=Q, transposed=cfg["transposed"])
-    kw.update(over)
-    return _lib.ScEngineLib.disco_desc(**kw)
-
-
-def _run(lib, cfg, x, w, psi, b, g, want=(True, True, True)):
-    """sc_disco_forward + sc_disco_backward on host tensors: (out, gx, gw, gbias)"""
-    d = _desc(cfg, g.shape[2:])
-    nbytes, fbytes = lib.disco_workspace_bytes(d), lib.disco_forward_workspace_bytes(d)
-    assert 0 < fbytes <= nbytes
-    ws = torch.empty(nbytes, dtype=torch.uint8)
-    y = torch.full(tuple(g.shape), float("nan"))
-    lib.disco_forward(d, x.data_ptr(), w.data_ptr(), psi.data_ptr(), 0 if b is None else b.data_ptr(), y.data_ptr(),
-                      ws.data_ptr(), fbytes)                 # its own, smaller size
-    gx = torch.full_like(x, float("nan")) if want[0] else None
-    gw = torch.full_like(w, float("nan")) if want[1] else None
-    gb = torch.full((cfg["c_out"],), float("nan")) if want[2] else None
-    ws.fill_(0xff)                                           # the backward call owes nothing to the forward call's workspace
-    lib.disco_backward(d, x.data_ptr(), w.data_ptr(), psi.data_ptr(), g.data_ptr(), *(0 if t is None else t.data_ptr()
-                                                                                        for t in (gx, gw, gb)),
-                       ws.data_ptr(), nbytes)
-    return y, gx, gw, gb
-
-
-def _want(cfg, x, w, psi, b, g):
-    out, gx, gw, gb = dr.disco_with_grads(x, w, b, psi, g, Q, cfg["stride"], cfg["padding"], cfg["opad"], cfg["groups"],
-                                          cfg["transposed"])
-    if gb is None:                                           # the bias gradient does not need a bias
-        gb = g.double().sum(dim=(0, 2, 3))
-    return out, gx, gw, gb
+# the descriptor runners and the case list live in disco_reference.py: the GPU tier drives them on the device
+_cfg, _inputs, _desc, _run, _want = dr.desc_case, dr.desc_inputs, dr.desc_of, dr.run_descriptor, dr.desc_want
+CASES, Q = dr.DESC_CASES, dr.Q
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -114,6 +33,23 @@ def test_both_routes_against_the_float64_helper(emu, name):
     errs = [dr.rel_l2(a.numpy(), t.numpy()) for a, t in zip(got, _want(cfg, x, w, psi, b, g))]
     print(name, " ".join(f"{e:.1e}" for e in errs))
     assert max(errs) <= 1e-5, errs
+
+
+@pytest.mark.parametrize("name", dr.EMU_KERNEL_CASES)
+def test_kernel_edge_cases_small_enough_for_the_emulation(emu, name):
+    """the cases of tests/test_gpu_disco_kernels.py that finish here in seconds, at that file's two bars: rel-L2 1e-5
+    per tensor and |got - want| <= gamma_N A per element (disco_reference.abs_bounds)"""
+    cfg = dr.KERNEL_CASES[name]
+    x, w, psi, b, g = _inputs(cfg, 91)
+    assert emu.disco_path(_desc(cfg, g.shape[2:])) == cfg["route"]
+    got = [t.numpy() for t in _run(emu, cfg, x, w, psi, b, g)]
+    want = [t.numpy() for t in _want(cfg, x, w, psi, b, g)]
+    errs = [dr.rel_l2(a, t) for a, t in zip(got, want)]
+    assert max(errs) <= 1e-5, errs
+    bounds, ns = dr.abs_bounds(cfg, x, w, psi, b, g)
+    ratios = [dr.worst_ratio(a, t, A.numpy(), n) for a, t, A, n in zip(got, want, bounds, ns)]
+    print(name, "worst |err| / (gamma_N A)", " ".join(f"{r:.3f}" for r in ratios))
+    assert max(ratios) <= 1.0, ratios
 
 
 @pytest.mark.parametrize("name", ["5x5_stride2", "transpose_strides_2x3_grouped", "mfma_32_32"])

@@ -40,6 +40,10 @@ def test_against_the_float64_helper(emu, name):
             for a, t in zip(got[:4], want)]
     print(name, " ".join(f"{e:.1e}" for e in errs))
     assert max(errs) <= 1e-5, errs
+    bounds, ns = ds.abs_bounds(cfg, psi, keep, x, w, q, b, g)            # per element: |got - want| <= gamma_N A
+    ratios = [ds.worst_ratio(a.numpy(), t.numpy(), A.numpy(), n) for a, t, A, n in zip(got[:4], want, bounds, ns)]
+    print(name, "worst |err| / (gamma_N A)", " ".join(f"{r:.3f}" for r in ratios))
+    assert max(ratios) <= 1.0, ratios
     z = torch.einsum("koi,bci->obkc", psi.double(), (q * x).double())    # the saved tensor in the engine's layout
     assert float(z.abs().max()) == 0 or ds.rel_l2(got[4].numpy(), z.numpy()) <= 1e-5
     for o, k in cfg["empty"]:                                            # an empty row writes zeros

@@ -17,25 +17,7 @@ def emu():
         yield lib
 
 
-def _desc(cfg, h):
-    return _lib.ScEngineLib.fdconv_desc(dims=cfg["dims"], batch=cfg["batch"], c_in=cfg["c_in"], c_out=cfg["c_out"],
-                                        k=cfg["k"], groups=cfg["groups"], padding=cfg["padding"], inv_h=1.0 / h)
-
-
-def _run(lib, cfg, x, w, g, h, want_x=True, want_w=True):
-    """sc_fdconv_forward + sc_fdconv_backward on host tensors: (out, gx, gw)"""
-    d = _desc(cfg, h)
-    nbytes, fbytes = lib.fdconv_workspace_bytes(d), lib.fdconv_forward_workspace_bytes(d)
-    assert 0 < fbytes <= nbytes
-    ws = torch.empty(nbytes, dtype=torch.uint8)
-    y = torch.full((cfg["batch"], cfg["c_out"], *cfg["dims"]), float("nan"))
-    lib.fdconv_forward(d, x.data_ptr(), w.data_ptr(), y.data_ptr(), ws.data_ptr(), fbytes)   # its own, smaller size
-    gx = torch.full_like(x, float("nan")) if want_x else None
-    gw = torch.full_like(w, float("nan")) if want_w else None
-    ws.fill_(0xff)                                           # the backward call owes nothing to the forward call's workspace
-    lib.fdconv_backward(d, x.data_ptr(), w.data_ptr(), g.data_ptr(), 0 if gx is None else gx.data_ptr(),
-                        0 if gw is None else gw.data_ptr(), ws.data_ptr(), nbytes)
-    return y, gx, gw
+_desc, _run = fr.desc_of, fr.run_descriptor             # the runner the GPU tier drives on the device
 
 
 ALL_CASES = {**fr.CASES, **fr.LIVE_CASES}
@@ -57,6 +39,23 @@ def test_both_routes_against_the_float64_helper(emu, name):
         print(name, "ratio to the fp32 formula's own error", " ".join(f"{2 * e / b:.2f}" for e, b in zip(errs, bars)))
     print(name, " ".join(f"{e:.1e}" for e in errs))
     assert not gw.numpy()[fr.centre_index(cfg)].any()
+
+
+@pytest.mark.parametrize("name", fr.EMU_KERNEL_CASES)
+def test_kernel_edge_cases_small_enough_for_the_emulation(emu, name):
+    """the cases of tests/test_gpu_fdconv_kernels.py that finish here in seconds, at that file's two bars: rel-L2 1e-5
+    per tensor and |got - want| <= gamma_N A per element (fdconv_reference.abs_bounds)"""
+    cfg = fr.KERNEL_CASES[name]
+    x, w, g = fr.case_inputs(cfg, 91)
+    h = fr.grid_width_of(cfg)
+    assert emu.fdconv_path(_desc(cfg, h)) == cfg["route"]
+    got = [t.numpy() for t in _run(emu, cfg, x, w, g, h)]
+    want = [t.numpy() for t in fr.fdconv_with_grads(x, w, g, h, cfg["groups"], cfg["padding"])]
+    fr.check_against(cfg, got, want, (1e-5, 1e-5, 1e-5), fr.magnitudes(x, w, g, h, cfg["groups"], cfg["padding"]))
+    bounds, ns = fr.abs_bounds(cfg, x, w, g, h)
+    ratios = [fr.worst_ratio(a, b, A, n) for a, b, A, n in zip(got, want, bounds, ns)]
+    print(name, "worst |err| / (gamma_N A)", " ".join(f"{r:.3f}" for r in ratios))
+    assert max(ratios) <= 1.0, ratios
 
 
 @pytest.mark.parametrize("name", ["2d_k3_replicate_g2", "2d_mfma_zeros_32_b1", "3d_k3_reflect"])
