@@ -391,6 +391,19 @@ int sc_radius_count(const sc_radius_desc* desc, const float* data, const float* 
 int sc_radius_fill(const sc_radius_desc* desc, const float* data, const float* queries, const int64_t* row_splits,
                    int64_t n_edges, int64_t* index, float* weights, void* stream);
 
+/* The same search over a uniform grid of cells at least radius wide: the data points are binned on the device (bounds,
+ * cell histogram, scan, slot scatter into cell order) and a query is tested against the points of its own and the
+ * adjacent cells only.  Same descriptor, same refusals, and the SAME BYTES out as the two calls above for every input:
+ * the hit test is the same fp32 expression, and each row is ranked into ascending data index.  The grid lives in ws
+ * (sc_radius_grid_workspace_bytes: a function of the descriptor alone, 0 for a bad one); a short or null workspace is
+ * refused before any launch.  sc_radius_grid_count builds the grid and counts; sc_radius_grid_fill reuses the grid
+ * the count pass left in the same ws.  The host reads nothing but row_splits[m]. */
+size_t sc_radius_grid_workspace_bytes(const sc_radius_desc* desc);
+int sc_radius_grid_count(const sc_radius_desc* desc, const float* data, const float* queries, int32_t* deg,
+                         int64_t* row_splits, void* ws, size_t ws_bytes, void* stream);
+int sc_radius_grid_fill(const sc_radius_desc* desc, const float* data, const float* queries, const int64_t* row_splits,
+                        int64_t n_edges, int64_t* index, float* weights, void* ws, size_t ws_bytes, void* stream);
+
 /* Transpose of any valid CSR graph (rows, cols, n_edges; the backward pass of integral_transform.py:167 f_y[:, idx]):
  * col_splits[cols + 1], perm[n_edges] = edge ids grouped by column, ascending within each group, row_of_edge[n_edges].
  * Integer atomics build a histogram and fill slots; one wave per column then ranks its slice, so the output does not

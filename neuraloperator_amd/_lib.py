@@ -267,7 +267,8 @@ class ScEngineLib:
                "sc_fdconv_forward", "sc_fdconv_backward", "sc_disco_path", "sc_disco_workspace_bytes",
                "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward", "sc_dsparse_path",
                "sc_dsparse_workspace_bytes", "sc_dsparse_forward_workspace_bytes", "sc_dsparse_forward",
-               "sc_dsparse_backward"]
+               "sc_dsparse_backward", "sc_radius_grid_workspace_bytes", "sc_radius_grid_count",
+               "sc_radius_grid_fill"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -429,6 +430,13 @@ class ScEngineLib:
         L.sc_lp_grad.restype = c_int
         L.sc_radius_count.argtypes = [POINTER(RadiusDesc)] + [c_void_p] * 5
         L.sc_radius_fill.argtypes = [POINTER(RadiusDesc), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+        L.sc_radius_grid_workspace_bytes.argtypes = [POINTER(RadiusDesc)]
+        L.sc_radius_grid_workspace_bytes.restype = c_size_t
+        L.sc_radius_grid_count.argtypes = [POINTER(RadiusDesc)] + [c_void_p] * 5 + [c_size_t, c_void_p]
+        L.sc_radius_grid_count.restype = c_int
+        L.sc_radius_grid_fill.argtypes = [POINTER(RadiusDesc), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]
+        L.sc_radius_grid_fill.restype = c_int
         L.sc_csr_transpose_workspace_bytes.argtypes = [POINTER(CsrDesc)]
         L.sc_csr_transpose_workspace_bytes.restype = c_size_t
         L.sc_csr_transpose.argtypes = [POINTER(CsrDesc)] + [c_void_p] * 6 + [c_size_t, c_void_p]
@@ -841,6 +849,21 @@ class ScEngineLib:
         """neighbors_index[n_edges] (ascending per query) and the squared distances (sc_radius_fill)"""
         self._check(self.lib.sc_radius_fill(byref(desc), data_ptr or None, queries_ptr or None, splits_ptr or None,
                                             n_edges, index_ptr or None, weights_ptr or None, stream))
+
+    def radius_grid_workspace_bytes(self, desc):
+        return int(self.lib.sc_radius_grid_workspace_bytes(byref(desc)))
+
+    def radius_grid_count(self, desc, data_ptr, queries_ptr, deg_ptr, splits_ptr, ws_ptr, ws_bytes, stream=0):
+        """radius_count over a uniform cell grid built in ws (sc_radius_grid_count)"""
+        self._check(self.lib.sc_radius_grid_count(byref(desc), data_ptr or None, queries_ptr or None, deg_ptr or None,
+                                                  splits_ptr or None, ws_ptr or None, ws_bytes, stream))
+
+    def radius_grid_fill(self, desc, data_ptr, queries_ptr, splits_ptr, n_edges, index_ptr, weights_ptr, ws_ptr, ws_bytes,
+                         stream=0):
+        """radius_fill over the grid the count pass left in ws (sc_radius_grid_fill)"""
+        self._check(self.lib.sc_radius_grid_fill(byref(desc), data_ptr or None, queries_ptr or None, splits_ptr or None,
+                                                 n_edges, index_ptr or None, weights_ptr or None, ws_ptr or None,
+                                                 ws_bytes, stream))
 
     @staticmethod
     def csr_desc(rows, cols, n_edges, n_splits=None):

@@ -1233,11 +1233,27 @@ def _gno_tensor(t, what, dtype=torch.float32, device=None):
     return t.contiguous()
 
 
-def radius_search(data, queries, radius, return_norm=False):
+RADIUS_METHODS = ("auto", "brute", "grid")
+# "auto" takes the cell grid from this many pair tests on, for at least RADIUS_GRID_MIN_POINTS data points
+RADIUS_GRID_MIN_PAIRS = 1 << 28
+RADIUS_GRID_MIN_POINTS = 4096
+
+
+def radius_route(n, m, d):
+    """The route method="auto" takes for n data points, m queries in d dimensions: "brute" or "grid".  A function of
+    the shape alone; both routes return the same bytes, so it decides the time and nothing else."""
+    return "grid" if int(n) * int(m) >= RADIUS_GRID_MIN_PAIRS and int(n) >= RADIUS_GRID_MIN_POINTS else "brute"
+
+
+def radius_search(data, queries, radius, return_norm=False, method="auto"):
     """Fixed-radius neighbours of every query among data (n, d), d = 1..3, as the reference's dict: neighbors_index
     int64 [E] (ascending per query), neighbors_row_splits int64 [m + 1], with return_norm weights fp32 [E] (squared
     distances, 1e-14 for coincident points).  Two passes (count + scan, fill); between them the host reads the edge
-    count -- one 8-byte copy, where the reference's nonzero() synchronises too."""
+    count -- one 8-byte copy, where the reference's nonzero() synchronises too.  method: "brute" tests every pair,
+    "grid" bins the data points into cells at least radius wide and tests the 3^d cells around a query, "auto" is
+    radius_route(n, m, d); the result is the same bytes on either."""
+    if method not in RADIUS_METHODS:
+        raise ValueError(f"neighbor search: method must be one of {RADIUS_METHODS}, got {method!r}")
     data = _gno_tensor(data.detach(), "data")
     queries = _gno_tensor(queries.detach(), "queries", device=data.device)
     if data.dim() != 2 or queries.dim() != 2 or data.shape[1] != queries.shape[1] or not 1 <= data.shape[1] <= 3:
@@ -1248,13 +1264,25 @@ def radius_search(data, queries, radius, return_norm=False):
     desc = lib.radius_desc(data.shape[1], n, m, radius, return_norm)
     deg = torch.empty(m, dtype=torch.int32, device=dev)
     splits = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    grid = (radius_route(n, m, data.shape[1]) if method == "auto" else method) == "grid"
     with torch.cuda.device(dev):
-        lib.radius_count(desc, data.data_ptr(), queries.data_ptr(), deg.data_ptr(), splits.data_ptr(), stream=_stream())
+        if grid:
+            ws_bytes = lib.radius_grid_workspace_bytes(desc)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            lib.radius_grid_count(desc, data.data_ptr(), queries.data_ptr(), deg.data_ptr(), splits.data_ptr(),
+                                  ws.data_ptr(), ws_bytes, stream=_stream())
+        else:
+            lib.radius_count(desc, data.data_ptr(), queries.data_ptr(), deg.data_ptr(), splits.data_ptr(),
+                             stream=_stream())
         n_edges = int(splits[m].item())
         index = torch.empty(n_edges, dtype=torch.int64, device=dev)
         weights = torch.empty(n_edges, dtype=torch.float32, device=dev) if return_norm else None
-        lib.radius_fill(desc, data.data_ptr(), queries.data_ptr(), splits.data_ptr(), n_edges, index.data_ptr(),
-                        0 if weights is None else weights.data_ptr(), stream=_stream())
+        if grid:
+            lib.radius_grid_fill(desc, data.data_ptr(), queries.data_ptr(), splits.data_ptr(), n_edges, index.data_ptr(),
+                                 0 if weights is None else weights.data_ptr(), ws.data_ptr(), ws_bytes, stream=_stream())
+        else:
+            lib.radius_fill(desc, data.data_ptr(), queries.data_ptr(), splits.data_ptr(), n_edges, index.data_ptr(),
+                            0 if weights is None else weights.data_ptr(), stream=_stream())
     out = {}
     if return_norm:
         out["weights"] = weights

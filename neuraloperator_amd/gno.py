@@ -73,15 +73,19 @@ class SinusoidalEmbedding(nn.Module):
 class NeighborSearch(nn.Module):
     """For each point of ``queries`` the indices of all points of ``data`` within ``radius``, in CSR form
     (neighbors_index int64, neighbors_row_splits int64 [m + 1], with return_norm also weights = squared distances).
-    ``use_open3d`` is accepted and ignored: the search is the engine's for d = 1, 2, 3."""
+    ``use_open3d`` is accepted and ignored: the search is the engine's for d = 1, 2, 3.  ``method``: "brute", "grid" (a
+    uniform cell grid) or "auto" (engine.radius_route by the shape); the result is the same bytes on either."""
 
-    def __init__(self, use_open3d=True, return_norm=False):
+    def __init__(self, use_open3d=True, return_norm=False, method="auto"):
         super().__init__()
+        if method not in engine.RADIUS_METHODS:
+            raise ValueError(f"neighbor search: method must be one of {engine.RADIUS_METHODS}, got {method!r}")
         self.use_open3d = False
         self.return_norm = return_norm
+        self.method = method
 
     def forward(self, data, queries, radius):
-        return engine.radius_search(data, queries, radius, self.return_norm)
+        return engine.radius_search(data, queries, radius, self.return_norm, self.method)
 
 
 def segment_csr(src, indptr, reduction, use_scatter=True):

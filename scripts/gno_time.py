@@ -1,12 +1,15 @@
 """The graph neural operator layer on one MI355X, for manual use (no test runs this):
 
-    python scripts/gno_time.py [--iters 50] [--out profiles/gno.txt]
+    python scripts/gno_time.py [--iters 50] [--out profiles/gno.txt] [--search-only]
 
 Per shape: the engine's radius search, first layer by point (sc_edge_lift) and fused reduce (sc_csr_reduce), each beside
 a device-to-device copy of its own algorithmic bytes, and a whole GNOBlock forward + backward beside the reference's
 formula written as a torch chain on the same GPU (dense cdist search, indexing, the MLP over edges, index_add_ in place of
 the Python loop of segment_csr).  Shapes: 3586 surface points against 32^3 and 64^3 grid queries at radius 0.033 (the
-GINO in direction) and the reverse (the out direction).  Events around the whole loop after a warm-up."""
+GINO in direction) and the reverse (the out direction).  Then the search alone on both routes (method="brute" and
+method="grid", the same bytes out): those four shapes, a synthetic 100 000-point surface against 64^3 in both directions,
+and a sweep over the number of data points at 64^3 queries that shows where the routes cross (engine.radius_route's
+threshold is set from it).  --search-only skips the first part.  Events around the whole loop after a warm-up."""
 import argparse
 import os
 import sys
@@ -58,16 +61,63 @@ def chain_block(block, y, x, f, chunk=8192):
     return torch.zeros(f.shape[0], x.shape[0], k.shape[-1], device=k.device).index_add_(1, rows, k)
 
 
+def sphere_surface(n, gen):
+    """n points on the sphere of radius 0.3 around the centre of the unit box: a closed surface mesh's worth of points"""
+    v = torch.randn(n, 3, generator=gen)
+    return (0.5 + 0.3 * v / v.norm(dim=1, keepdim=True)).float().contiguous()
+
+
+def lattice_grid(res, dev):
+    ax = torch.linspace(0, 1, res)
+    return torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3).to(dev)
+
+
+def search_routes(lines, tag, y, x, iters):
+    """one row: the search alone on both routes, after checking that they return the same bytes"""
+    a = engine.radius_search(y, x, RADIUS, True, method="brute")
+    b = engine.radius_search(y, x, RADIUS, True, method="grid")
+    assert all(torch.equal(a[k], b[k]) for k in a), tag
+    n, m = y.shape[0], x.shape[0]
+    it = max(3, min(iters, int(2e11 / (n * m))))            # the brute-force route at 2.6e10 pair tests takes a while
+    t_b = timed(lambda: engine.radius_search(y, x, RADIUS, True, method="brute"), it, warmup=2)
+    t_g = timed(lambda: engine.radius_search(y, x, RADIUS, True, method="grid"), it, warmup=2)
+    lines.append(f"{tag:>22s} {n:8d} {m:8d} {n * m:10.3g} {a['neighbors_index'].numel():9d} {t_b:10.1f} {t_g:10.1f} "
+                 f"{t_b / t_g:7.2f}  {engine.radius_route(n, m, 3)}")
+    print(lines[-1], flush=True)
+
+
+def search_table(dev, iters):
+    g = torch.Generator().manual_seed(0)
+    surf = (0.25 + 0.5 * torch.rand(N_SURF, 3, generator=g)).to(dev)
+    lines = ["", "search alone, both routes (weights included; the host's 8-byte read of the edge count is inside)",
+             f"{'shape':>22s} {'n':>8s} {'m':>8s} {'n*m':>10s} {'edges':>9s} {'brute us':>10s} {'grid us':>10s} "
+             f"{'b/g':>7s}  auto"]
+    for res in (32, 64):
+        grid = lattice_grid(res, dev)
+        search_routes(lines, f"in {N_SURF}->{res}^3", surf, grid, iters)
+        search_routes(lines, f"out {res}^3->{N_SURF}", grid, surf, iters)
+    big, grid = sphere_surface(100_000, g).to(dev), lattice_grid(64, dev)
+    search_routes(lines, "in 100000->64^3", big, grid, iters)
+    search_routes(lines, "out 64^3->100000", grid, big, iters)
+    lines += ["", "crossover sweep: n surface points against m grid queries"]
+    for res in (32, 64):
+        grid = lattice_grid(res, dev)
+        for n in (256, 512, 1024, 2048, 4096, 8192, 16384, 32768):
+            search_routes(lines, f"sweep {n}->{res}^3", sphere_surface(n, g).to(dev), grid, iters)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--search-only", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     surf = (0.25 + 0.5 * torch.rand(N_SURF, 3, generator=g)).to(dev)
     lines = [f"{'shape':>22s} {'step':>14s} {'engine us':>10s} {'copy us':>9s} {'torch chain us':>15s}"]
-    for res in (32, 64):
+    for res in (() if args.search_only else (32, 64)):
         ax = torch.linspace(0, 1, res)
         grid = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3).to(dev)
         for tag, y, x in ((f"in {N_SURF}->{res}^3", surf, grid), (f"out {res}^3->{N_SURF}", grid, surf)):
@@ -98,6 +148,7 @@ def main():
                 lines.append(f"{tag:>22s} {name:>14s} {t_eng:10.1f} {t_copy:9.1f} {t_ref:15.1f}")
                 print(lines[-1], flush=True)
             lines.append(f"{tag:>22s} {'edges':>14s} {E:10d}")
+    lines += search_table(dev, args.iters)
     text = "\n".join(lines) + "\n"
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
