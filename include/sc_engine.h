@@ -459,6 +459,43 @@ int sc_edge_lift(const sc_edge_lift_desc* desc, const float* Py, const float* Px
 int sc_edge_lift_bwd(const sc_edge_lift_desc* desc, const float* Py, const float* Px, const float* bias,
                      const float* gH, float* gPre, void* stream);
 
+/* The whole kernel MLP over CHUNKS of edges (LinearChannelMLP with GELU of n_layers >= 2 Linear layers, channel_mlp.py):
+ *   h_0 = gelu(Py[(b,) index[e]] + Px[row(e)] + bias0)            widths[0] channels, never stored for all edges
+ *   h_l = gelu(h_{l-1} W_l^T + b_l), l = 1 .. n_layers - 2        W_l (widths[l], widths[l-1]) row-major
+ *   K[(b,) e] = h_{L-2} W_{L-1}^T + b_{L-1}                        widths[L-1] channels
+ * W / b / gW / gb are HOST arrays of n_layers - 1 device pointers (entry l - 1 belongs to layer l; a null b entry means
+ * no bias, a null gW / gb entry not wanted).  One call walks the edges in chunks of chunk_edges (a multiple of
+ * SC_EDGE_MLP_TILE; 0 = the default) with stream-ordered launches and no host wait; the workspace of
+ * sc_edge_mlp_workspace_bytes(desc) depends on widths, batch and chunk_edges alone, not on n_edges.
+ * sc_edge_mlp_backward recomputes the chain per chunk and ADDS each chunk's share into gPy ((b,) n_py, widths[0]), gPx
+ * (rows, widths[0]), gW_l and gb_l, which it zero-fills first; it needs col_splits / perm of sc_csr_transpose when gPy
+ * is wanted.  row(e) is found by a binary search in splits; row_of_edge is accepted and not read.  An index[e] outside
+ * [0, n_py) gives h_0 = 0 for that edge and no gradient.  Deterministic: no float atomics, fixed-order sums.
+ * Refused before any launch: n_layers outside 2 .. 8, a width outside 1 .. 512, a chunk_edges that is no multiple of the
+ * tile, a workspace that is too small, a null pointer.  n_edges = 0: no launch (backward: the zero gradients alone). */
+#define SC_EDGE_MLP_MAX_LAYERS 8
+#define SC_EDGE_MLP_MAX_WIDTH 512
+#define SC_EDGE_MLP_TILE 128
+typedef struct {
+  int64_t rows, n_splits, n_edges, n_py;
+  int64_t py_batch_stride;     /* floats; 0: Py (n_py, c) and batch = 1 */
+  int64_t chunk_edges;
+  int32_t batch, n_layers;
+  int32_t widths[SC_EDGE_MLP_MAX_LAYERS];
+  const int64_t* splits;
+  const int64_t* index;
+  const int32_t* row_of_edge;  /* optional */
+  const int64_t* col_splits;   /* backward */
+  const int32_t* perm;         /* backward */
+} sc_edge_mlp_desc;
+size_t sc_edge_mlp_workspace_bytes(const sc_edge_mlp_desc* desc);
+int sc_edge_mlp_forward(const sc_edge_mlp_desc* desc, const float* Py, const float* Px, const float* bias0,
+                        const float* const* W, const float* const* b, float* K, void* ws, size_t ws_bytes,
+                        void* stream);
+int sc_edge_mlp_backward(const sc_edge_mlp_desc* desc, const float* Py, const float* Px, const float* bias0,
+                         const float* const* W, const float* const* b, const float* gK, float* gPy, float* gPx,
+                         float* const* gW, float* const* gb, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- finite-difference convolution of the local neural operator (neuralop/layers/differential_conv.py:6-101) ----
  *   y = (conv_pad(x, W) - conv_1x1(x, sum_taps W)) * inv_h
  * as ONE convolution with folded weights: W'[.., t] = W[.., t] inv_h off the centre, W'[.., centre] = -(sum of the other

@@ -168,6 +168,15 @@ class EdgeLiftDesc(Structure):                              # sc_edge_lift_desc
 
 SC_LIFT_IDENTITY, SC_LIFT_GELU = 0, 1
 
+SC_EDGE_MLP_MAX_LAYERS, SC_EDGE_MLP_MAX_WIDTH, SC_EDGE_MLP_TILE = 8, 512, 128
+
+
+class EdgeMlpDesc(Structure):                               # sc_edge_mlp_desc
+    _fields_ = [("rows", c_int64), ("n_splits", c_int64), ("n_edges", c_int64), ("n_py", c_int64),
+                ("py_batch_stride", c_int64), ("chunk_edges", c_int64), ("batch", c_int32), ("n_layers", c_int32),
+                ("widths", c_int32 * SC_EDGE_MLP_MAX_LAYERS), ("splits", c_void_p), ("index", c_void_p),
+                ("row_of_edge", c_void_p), ("col_splits", c_void_p), ("perm", c_void_p)]
+
 
 class FdconvDesc(Structure):                                # sc_fdconv_desc
     _fields_ = [("ndim", c_int32), ("k", c_int32), ("padding", c_int32), ("groups", c_int32), ("dims", c_int64 * 3),
@@ -268,7 +277,7 @@ class ScEngineLib:
                "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward", "sc_dsparse_path",
                "sc_dsparse_workspace_bytes", "sc_dsparse_forward_workspace_bytes", "sc_dsparse_forward",
                "sc_dsparse_backward", "sc_radius_grid_workspace_bytes", "sc_radius_grid_count",
-               "sc_radius_grid_fill"]
+               "sc_radius_grid_fill", "sc_edge_mlp_workspace_bytes", "sc_edge_mlp_forward", "sc_edge_mlp_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -447,6 +456,12 @@ class ScEngineLib:
         for s in ("sc_radius_count", "sc_radius_fill", "sc_csr_transpose", "sc_csr_reduce", "sc_csr_edge_grad",
                   "sc_edge_lift", "sc_edge_lift_bwd"):
             getattr(L, s).restype = c_int
+        L.sc_edge_mlp_workspace_bytes.argtypes = [POINTER(EdgeMlpDesc)]
+        L.sc_edge_mlp_workspace_bytes.restype = c_size_t
+        L.sc_edge_mlp_forward.argtypes = [POINTER(EdgeMlpDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]
+        L.sc_edge_mlp_forward.restype = c_int
+        L.sc_edge_mlp_backward.argtypes = [POINTER(EdgeMlpDesc)] + [c_void_p] * 11 + [c_size_t, c_void_p]
+        L.sc_edge_mlp_backward.restype = c_int
         L.sc_fdconv_path.argtypes = [POINTER(FdconvDesc)]
         L.sc_fdconv_path.restype = c_int
         L.sc_fdconv_workspace_bytes.argtypes = [POINTER(FdconvDesc)]
@@ -916,6 +931,42 @@ class ScEngineLib:
         """gPre = gH act'(pre), the pre-activation recomputed (sc_edge_lift_bwd)"""
         self._check(self.lib.sc_edge_lift_bwd(byref(desc), py_ptr or None, px_ptr or None, bias_ptr or None,
                                               gh_ptr or None, gpre_ptr or None, stream))
+
+    @staticmethod
+    def edge_mlp_desc(*, rows, n_edges, n_py, widths, splits, index, batch=1, py_batch_stride=0, chunk_edges=0,
+                      row_of_edge=0, col_splits=0, perm=0, n_layers=None, n_splits=None):
+        """widths: the output channels of the n_layers Linear layers, the point-wise layer 0 first"""
+        d = EdgeMlpDesc()
+        d.rows, d.n_edges, d.n_py, d.batch = int(rows), int(n_edges), int(n_py), int(batch)
+        d.n_splits = int(rows) + 1 if n_splits is None else int(n_splits)
+        d.py_batch_stride, d.chunk_edges = int(py_batch_stride), int(chunk_edges)
+        d.n_layers = len(widths) if n_layers is None else int(n_layers)
+        for i, w in enumerate(list(widths)[:SC_EDGE_MLP_MAX_LAYERS]):
+            d.widths[i] = int(w)
+        d.splits, d.index, d.row_of_edge = splits or None, index or None, row_of_edge or None
+        d.col_splits, d.perm = col_splits or None, perm or None
+        return d
+
+    def edge_mlp_workspace_bytes(self, desc):
+        return int(self.lib.sc_edge_mlp_workspace_bytes(byref(desc)))
+
+    @staticmethod
+    def _ptr_array(ptrs):
+        return (c_void_p * max(len(ptrs), 1))(*[p or None for p in ptrs])
+
+    def edge_mlp_forward(self, desc, py_ptr, px_ptr, bias0_ptr, w_ptrs, b_ptrs, k_ptr, ws_ptr, ws_bytes, stream=0):
+        """K = the kernel MLP over chunks of edges (sc_edge_mlp_forward); w_ptrs / b_ptrs: device pointers of layers 1 .."""
+        self._check(self.lib.sc_edge_mlp_forward(byref(desc), py_ptr or None, px_ptr or None, bias0_ptr or None,
+                                                 self._ptr_array(w_ptrs), self._ptr_array(b_ptrs), k_ptr or None,
+                                                 ws_ptr or None, ws_bytes, stream))
+
+    def edge_mlp_backward(self, desc, py_ptr, px_ptr, bias0_ptr, w_ptrs, b_ptrs, gk_ptr, gpy_ptr, gpx_ptr, gw_ptrs,
+                          gb_ptrs, ws_ptr, ws_bytes, stream=0):
+        """gPy, gPx, gW_l, gb_l of the kernel MLP, the chain recomputed per chunk (sc_edge_mlp_backward)"""
+        self._check(self.lib.sc_edge_mlp_backward(byref(desc), py_ptr or None, px_ptr or None, bias0_ptr or None,
+                                                  self._ptr_array(w_ptrs), self._ptr_array(b_ptrs), gk_ptr or None,
+                                                  gpy_ptr or None, gpx_ptr or None, self._ptr_array(gw_ptrs),
+                                                  self._ptr_array(gb_ptrs), ws_ptr or None, ws_bytes, stream))
 
     @staticmethod
     def fdconv_desc(*, dims, batch, c_in, c_out, k, groups=1, padding="periodic", inv_h=1.0):

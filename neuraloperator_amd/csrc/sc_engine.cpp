@@ -53,6 +53,7 @@
 #include "sc_host_modegemm.h"
 #include "sc_host_gno.h"
 #include "sc_host_gno_grid.h"
+#include "sc_host_gno_mlp.h"
 #include "sc_host_fdconv.h"
 #include "sc_host_disco.h"
 #include "sc_host_disco_sparse.h"

@@ -1465,6 +1465,105 @@ class EdgeLiftFn(torch.autograd.Function):
         return gPy, gPx, gb, None, None
 
 
+EDGE_MLP_MAX_WIDTH = _lib.SC_EDGE_MLP_MAX_WIDTH
+EDGE_MLP_MAX_LAYERS = _lib.SC_EDGE_MLP_MAX_LAYERS
+# kernel_route="auto" of IntegralTransform takes the fused route from this many E * b * sum(widths) on; None: never, the
+# fused route is opt-in (DESIGN 3.22 has the measurements behind the choice)
+EDGE_MLP_AUTO_MIN_WORK = None
+# edges per chunk of the fused route, a multiple of 128; 0: the engine's default (sc_host_gno_mlp.h)
+EDGE_MLP_CHUNK_EDGES = 0
+
+
+def edge_mlp_route(n_edges, batch, widths):
+    """The route kernel_route="auto" takes for a kernel MLP of these layer widths over n_edges edges: "edges" (one
+    tensor per layer over all edges) or "fused" (EdgeMlpFn).  A function of the shape alone."""
+    if EDGE_MLP_AUTO_MIN_WORK is None:
+        return "edges"
+    return "fused" if int(n_edges) * int(batch) * sum(int(w) for w in widths) >= EDGE_MLP_AUTO_MIN_WORK else "edges"
+
+
+class EdgeMlpFn(torch.autograd.Function):
+    """K[(b,) e] = the kernel MLP on gelu(Py[(b,) index[e]] + Px[row(e)] + bias0), layers 1 .. as (W_l, b_l) pairs with
+    GELU between them (sc_edge_mlp_forward): one node for the whole chain, walked in chunks of edges through a workspace
+    that does not grow with the edge count.  It saves its inputs alone -- point-sized tensors and parameters; backward is
+    one sc_edge_mlp_backward call that recomputes each chunk.  ``calls`` counts the forward passes (tests)."""
+
+    calls = 0
+
+    @staticmethod
+    def _desc(graph, Py, widths, chunk_edges, transposed):
+        pb = Py.dim() == 3
+        kw = {}
+        if transposed:
+            col_splits, perm, row = graph.transpose()
+            kw = dict(col_splits=col_splits.data_ptr(), perm=perm.data_ptr(), row_of_edge=row.data_ptr())
+        return _lib.ScEngineLib.edge_mlp_desc(
+            rows=graph.rows, n_edges=graph.n_edges, n_py=graph.cols, widths=widths, splits=graph.splits.data_ptr(),
+            index=graph.index.data_ptr(), batch=int(Py.shape[0]) if pb else 1,
+            py_batch_stride=graph.cols * int(Py.shape[-1]) if pb else 0, chunk_edges=chunk_edges, **kw)
+
+    @staticmethod
+    def forward(ctx, Py, Px, bias0, graph, chunk_edges, *wb):
+        dev = graph.device
+        Py, Px = _gno_tensor(Py, "Py", device=dev), _gno_tensor(Px, "Px", device=dev)
+        if bias0 is not None:
+            bias0 = _gno_tensor(bias0, "bias", device=dev)
+        if len(wb) % 2 or not wb:
+            raise ValueError("gno: the later layers of the kernel MLP come as (weight, bias) pairs, at least one")
+        Ws = [_gno_tensor(w, "weight", device=dev) for w in wb[0::2]]
+        bs = [None if b is None else _gno_tensor(b, "bias", device=dev) for b in wb[1::2]]
+        c = int(Px.shape[-1])
+        widths = [c] + [int(w.shape[0]) for w in Ws]
+        if Px.shape != (graph.rows, c) or Py.shape[-2:] != (graph.cols, c) or Py.dim() not in (2, 3) or \
+                (bias0 is not None and bias0.shape != (c,)):
+            raise ValueError(f"gno: kernel MLP on Py {tuple(Py.shape)}, Px {tuple(Px.shape)} and a graph of {graph.rows} "
+                             f"rows, {graph.cols} columns")
+        for l, (w, b) in enumerate(zip(Ws, bs)):
+            if w.dim() != 2 or w.shape[1] != widths[l] or (b is not None and b.shape != (widths[l + 1],)):
+                raise ValueError(f"gno: layer {l + 1} of the kernel MLP has weight {tuple(w.shape)} after {widths[l]} channels")
+        ctx.graph, ctx.widths, ctx.chunk_edges = graph, widths, int(chunk_edges)
+        ctx.save_for_backward(Py, Px, bias0, *Ws, *bs)
+        EdgeMlpFn.calls += 1
+        lib = _lib.get_lib()
+        desc = EdgeMlpFn._desc(graph, Py, widths, ctx.chunk_edges, False)
+        K = torch.empty((*Py.shape[:-2], graph.n_edges, widths[-1]), dtype=torch.float32, device=dev)
+        nbytes = lib.edge_mlp_workspace_bytes(desc)
+        if nbytes == 0:
+            raise _lib.EngineError(lib.lib.sc_last_error().decode())
+        ws = _ws(nbytes, dev)
+        with torch.cuda.device(dev):
+            lib.edge_mlp_forward(desc, Py.data_ptr(), Px.data_ptr(), 0 if bias0 is None else bias0.data_ptr(),
+                                 [w.data_ptr() for w in Ws], [0 if b is None else b.data_ptr() for b in bs],
+                                 K.data_ptr(), ws.data_ptr(), nbytes, stream=_stream())
+        return K
+
+    @staticmethod
+    def backward(ctx, gK):
+        saved = ctx.saved_tensors
+        n = len(ctx.widths) - 1
+        Py, Px, bias0, Ws, bs = saved[0], saved[1], saved[2], saved[3:3 + n], saved[3 + n:3 + 2 * n]
+        gK = gK.float().contiguous()
+        dev = gK.device
+        lib = _lib.get_lib()
+        desc = EdgeMlpFn._desc(ctx.graph, Py, ctx.widths, ctx.chunk_edges, ctx.graph.n_edges > 0)
+        gPy, gPx = torch.empty_like(Py), torch.empty_like(Px)
+        gWs = [torch.empty_like(w) for w in Ws]
+        gbs = [None if b is None else torch.empty_like(b) for b in bs]
+        nbytes = lib.edge_mlp_workspace_bytes(desc)
+        ws = _ws(nbytes, dev)
+        with torch.cuda.device(dev):
+            lib.edge_mlp_backward(desc, Py.data_ptr(), Px.data_ptr(), 0 if bias0 is None else bias0.data_ptr(),
+                                  [w.data_ptr() for w in Ws], [0 if b is None else b.data_ptr() for b in bs],
+                                  gK.data_ptr(), gPy.data_ptr(), gPx.data_ptr(), [g.data_ptr() for g in gWs],
+                                  [0 if g is None else g.data_ptr() for g in gbs], ws.data_ptr(), nbytes,
+                                  stream=_stream())
+        gb0 = gPx.sum(0) if bias0 is not None and ctx.needs_input_grad[2] else None
+        out = [gPy, gPx, gb0, None, None]
+        for gw, gb in zip(gWs, gbs):
+            out += [gw, gb]
+        return tuple(out)
+
+
 class SegmentCsrFn(torch.autograd.Function):
     """out[(b,) i] = sum (or mean) of src[(b,) e] over row i (sc_csr_reduce with K = src)"""
 

@@ -4,9 +4,14 @@ Same constructors, forward signatures, return keys and errors as neuralop/layers
 integral_transform.py and gno_block.py; ``state_dict()`` keys and shapes equal the reference's.  The neighbour search is
 sc_radius_count / sc_radius_fill, the gather + products + segment reduction of the kernel integral one sc_csr_reduce,
 and -- where the kernel MLP is a LinearChannelMLP with GELU (or a single layer) -- its first Linear is applied to points
-instead of edges and sc_edge_lift forms the first hidden layer (sc_kernels_gno.h).  The remaining Linear layers run as
-F.linear over edges.  fp32 on a ROCm device only; there is no CPU path.
+instead of edges and sc_edge_lift forms the first hidden layer (sc_kernels_gno.h).  The remaining Linear layers run on
+one of two routes (``kernel_route``): "edges", F.linear over edge-sized tensors, or "fused", engine.EdgeMlpFn -- the
+whole chain in chunks of edges on sc_edge_mlp_forward / sc_edge_mlp_backward (sc_kernels_gno_mlp.h), which keeps no
+tensor of E x hidden width, forward or backward.  "auto" is engine.edge_mlp_route by the shape.  fp32 on a ROCm device
+only; there is no CPU path.
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -14,6 +19,22 @@ from torch import nn
 from . import engine
 
 TRANSFORM_TYPES = ("linear_kernelonly", "linear", "nonlinear_kernelonly", "nonlinear")
+KERNEL_ROUTES = ("auto", "edges", "fused")
+_ROUTE_OVERRIDE = None
+
+
+@contextlib.contextmanager
+def kernel_route(name):
+    """Inside the block every IntegralTransform takes this route for its kernel MLP, whatever it was built with:
+    "edges", "fused" (ValueError at a layer that is not eligible) or "auto"."""
+    global _ROUTE_OVERRIDE
+    if name not in KERNEL_ROUTES:
+        raise ValueError(f"IntegralTransform: kernel_route must be one of {KERNEL_ROUTES}, got {name!r}")
+    saved, _ROUTE_OVERRIDE = _ROUTE_OVERRIDE, name
+    try:
+        yield
+    finally:
+        _ROUTE_OVERRIDE = saved
 
 
 class LinearChannelMLP(nn.Module):
@@ -103,12 +124,17 @@ def segment_csr(src, indptr, reduction, use_scatter=True):
 class IntegralTransform(nn.Module):
     """Integral kernel transform (GNO): (a) int k(x, y) dy, (b) int k(x, y) f(y) dy, (c) int k(x, y, f(y)) dy,
     (d) int k(x, y, f(y)) f(y) dy for transform_type linear_kernelonly / linear / nonlinear_kernelonly / nonlinear.
-    ``use_torch_scatter`` is accepted and ignored."""
+    ``use_torch_scatter`` is accepted and ignored.  ``kernel_route``: "edges", "fused" or "auto" (see the module's
+    header); the context manager kernel_route() overrides it."""
 
     def __init__(self, channel_mlp=None, channel_mlp_layers=None, channel_mlp_non_linearity=F.gelu,
-                 transform_type="linear", weighting_fn=None, reduction="sum", use_torch_scatter=True):
+                 transform_type="linear", weighting_fn=None, reduction="sum", use_torch_scatter=True,
+                 kernel_route="auto"):
         super().__init__()
         assert channel_mlp is not None or channel_mlp_layers is not None
+        if kernel_route not in KERNEL_ROUTES:
+            raise ValueError(f"IntegralTransform: kernel_route must be one of {KERNEL_ROUTES}, got {kernel_route!r}")
+        self.kernel_route = kernel_route
         self.reduction = reduction
         self.transform_type = transform_type
         self.use_torch_scatter = use_torch_scatter
@@ -128,8 +154,28 @@ class IntegralTransform(nn.Module):
         return (isinstance(mlp, LinearChannelMLP) and mlp.dropout is None
                 and (mlp.n_layers == 1 or mlp.non_linearity is F.gelu))
 
+    def fused_eligible(self):
+        """True where the whole kernel MLP can run in chunks of edges (engine.EdgeMlpFn): the first layer on points, at
+        least two layers, GELU between them, no width above engine.EDGE_MLP_MAX_WIDTH"""
+        mlp = self.channel_mlp
+        return (self.lift_route() and 2 <= mlp.n_layers <= engine.EDGE_MLP_MAX_LAYERS
+                and all(fc.out_features <= engine.EDGE_MLP_MAX_WIDTH for fc in mlp.fcs))
+
+    def _route(self, n_edges, batch):
+        want = _ROUTE_OVERRIDE or self.kernel_route
+        if want == "fused" and not self.fused_eligible():
+            raise ValueError("IntegralTransform: kernel_route='fused' needs a LinearChannelMLP of 2 to "
+                             f"{engine.EDGE_MLP_MAX_LAYERS} layers with GELU, no dropout and widths of at most "
+                             f"{engine.EDGE_MLP_MAX_WIDTH}")
+        if want == "auto":
+            want = "edges"
+            if self.fused_eligible():
+                want = engine.edge_mlp_route(n_edges, batch, [fc.out_features for fc in self.channel_mlp.fcs])
+        return want
+
     def _kernel(self, y, x, f_y, graph, nonlinear):
         mlp = self.channel_mlp
+        route = self._route(graph.n_edges, f_y.shape[0] if nonlinear and f_y.ndim == 3 else 1)
         if self.lift_route():
             fc0, dy, dx = mlp.fcs[0], y.shape[-1], x.shape[-1]
             want = dy + dx + (f_y.shape[-1] if nonlinear else 0)
@@ -139,6 +185,9 @@ class IntegralTransform(nn.Module):
             Px = F.linear(x, fc0.weight[:, dy:dy + dx])
             if nonlinear:
                 Py = Py + F.linear(f_y, fc0.weight[:, dy + dx:])
+            if route == "fused":
+                later = [t for fc in mlp.fcs[1:] for t in (fc.weight, fc.bias)]
+                return engine.EdgeMlpFn.apply(Py, Px, fc0.bias, graph, engine.EDGE_MLP_CHUNK_EDGES, *later)
             h = engine.EdgeLiftFn.apply(Py, Px, fc0.bias, graph, mlp.n_layers > 1)
             for i in range(1, mlp.n_layers):
                 h = mlp.fcs[i](h)
@@ -227,7 +276,8 @@ class GNOBlock(nn.Module):
             channel_mlp = LinearChannelMLP(layers=channel_mlp_layers, non_linearity=channel_mlp_non_linearity)
         self.integral_transform = IntegralTransform(channel_mlp=channel_mlp, transform_type=transform_type,
                                                     use_torch_scatter=use_torch_scatter_reduce,
-                                                    weighting_fn=weighting_fn, reduction=reduction)
+                                                    weighting_fn=weighting_fn, reduction=reduction,
+                                                    kernel_route="auto")
 
     def forward(self, y, x, f_y=None):
         neighbors = self.neighbor_search(data=y, queries=x, radius=self.radius)

@@ -9,7 +9,11 @@ the Python loop of segment_csr).  Shapes: 3586 surface points against 32^3 and 6
 GINO in direction) and the reverse (the out direction).  Then the search alone on both routes (method="brute" and
 method="grid", the same bytes out): those four shapes, a synthetic 100 000-point surface against 64^3 in both directions,
 and a sweep over the number of data points at 64^3 queries that shows where the routes cross (engine.radius_route's
-threshold is set from it).  --search-only skips the first part.  Events around the whole loop after a warm-up."""
+threshold is set from it).  --search-only skips the first part.  --mlp adds (and --mlp-only runs alone) the kernel
+MLP's two routes: a GNOBlock forward + backward on kernel_route "edges" and "fused" with the peak of
+torch.cuda.max_memory_allocated of each, at those six shapes for the widths [80, 80, 80] and [512, 256], and the fused
+route's chunk size at the 3.76 M-edge shape for workspaces of 16 / 32 / 64 / 128 MiB (engine.edge_mlp_route and the
+default chunk are set from this table).  Events around the whole loop after a warm-up."""
 import argparse
 import os
 import sys
@@ -19,6 +23,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuraloperator_amd import GNOBlock, engine  # noqa: E402
+from neuraloperator_amd.gno import kernel_route  # noqa: E402
 
 N_SURF, RADIUS, CH = 3586, 0.033, 32
 
@@ -107,17 +112,87 @@ def search_table(dev, iters):
     return lines
 
 
+MLP_WIDTHS = ([80, 80, 80], [512, 256])
+
+
+def block_step(block, y, x, f, nbrs, route):
+    """forward + backward of the block's transform on precomputed neighbours (the search is the same on both routes)"""
+    f.grad = None
+    block.zero_grad(set_to_none=True)
+    ye, xe = block.pos_embedding(y), block.pos_embedding(x)
+    with kernel_route(route):
+        block.integral_transform(y=ye, x=xe, neighbors=nbrs, f_y=f).sum().backward()
+
+
+def mlp_routes(lines, tag, y, x, widths, iters):
+    """one row: both routes of the kernel MLP, time and peak memory of a step, and what "auto" takes"""
+    dev = y.device
+    nbrs = engine.radius_search(y, x, RADIUS)
+    E = nbrs["neighbors_index"].numel()
+    block = GNOBlock(CH, CH, 3, RADIUS, channel_mlp_layers=list(widths)).to(dev)
+    f = torch.randn(1, y.shape[0], CH, device=dev, requires_grad=True)
+    it = max(3, min(iters, int(3e7 / max(E, 1))))
+    out = {}
+    for route in ("edges", "fused"):
+        block_step(block, y, x, f, nbrs, route)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t = timed(lambda: block_step(block, y, x, f, nbrs, route), it, warmup=1)
+        out[route] = (t, torch.cuda.max_memory_allocated(dev) / 2 ** 20)
+    work = E * sum(list(widths) + [CH])
+    lines.append(f"{tag:>22s} {str(list(widths)):>14s} {E:9d} {work:10.3g} {out['edges'][0]:10.1f} {out['fused'][0]:10.1f} "
+                 f"{out['edges'][0] / out['fused'][0]:7.2f} {out['edges'][1]:10.1f} {out['fused'][1]:10.1f}  "
+                 f"{engine.edge_mlp_route(E, 1, list(widths) + [CH])}")
+    print(lines[-1], flush=True)
+
+
+def mlp_table(dev, iters):
+    g = torch.Generator().manual_seed(0)
+    surf = (0.25 + 0.5 * torch.rand(N_SURF, 3, generator=g)).to(dev)
+    lines = ["", "kernel MLP, both routes: the transform's forward + backward on precomputed neighbours, b = 1, 32 channels",
+             f"{'shape':>22s} {'widths':>14s} {'edges':>9s} {'E sum c':>10s} {'edges us':>10s} {'fused us':>10s} "
+             f"{'e/f':>7s} {'edges MiB':>10s} {'fused MiB':>10s}  auto"]
+    shapes = []
+    for res in (32, 64):
+        grid = lattice_grid(res, dev)
+        shapes += [(f"in {N_SURF}->{res}^3", surf, grid), (f"out {res}^3->{N_SURF}", grid, surf)]
+    big, grid = sphere_surface(100_000, g).to(dev), lattice_grid(64, dev)
+    shapes += [("in 100000->64^3", big, grid), ("out 64^3->100000", grid, big)]
+    for widths in MLP_WIDTHS:
+        for tag, y, x in shapes:
+            mlp_routes(lines, tag, y, x, widths, iters)
+    lines += ["", "fused route, chunk size at in 100000->64^3 (workspace of the hidden layers; 0 = the default)",
+              f"{'widths':>14s} {'workspace MiB':>14s} {'chunk_edges':>12s} {'fused us':>10s} {'peak MiB':>10s}"]
+    nbrs = engine.radius_search(big, grid, RADIUS)
+    for widths in MLP_WIDTHS:
+        block = GNOBlock(CH, CH, 3, RADIUS, channel_mlp_layers=list(widths)).to(dev)
+        f = torch.randn(1, big.shape[0], CH, device=dev, requires_grad=True)
+        for mib in (0, 16, 32, 64, 128):
+            engine.EDGE_MLP_CHUNK_EDGES = (mib << 20) // (8 * sum(widths)) // 128 * 128
+            block_step(block, big, grid, f, nbrs, "fused")
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            t = timed(lambda: block_step(block, big, grid, f, nbrs, "fused"), 3, warmup=1)
+            lines.append(f"{str(list(widths)):>14s} {mib:14d} {engine.EDGE_MLP_CHUNK_EDGES:12d} {t:10.1f} "
+                         f"{torch.cuda.max_memory_allocated(dev) / 2 ** 20:10.1f}")
+            print(lines[-1], flush=True)
+        engine.EDGE_MLP_CHUNK_EDGES = 0
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--search-only", action="store_true")
+    ap.add_argument("--mlp", action="store_true")
+    ap.add_argument("--mlp-only", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     surf = (0.25 + 0.5 * torch.rand(N_SURF, 3, generator=g)).to(dev)
     lines = [f"{'shape':>22s} {'step':>14s} {'engine us':>10s} {'copy us':>9s} {'torch chain us':>15s}"]
-    for res in (() if args.search_only else (32, 64)):
+    for res in (() if args.search_only or args.mlp_only else (32, 64)):
         ax = torch.linspace(0, 1, res)
         grid = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3).to(dev)
         for tag, y, x in ((f"in {N_SURF}->{res}^3", surf, grid), (f"out {res}^3->{N_SURF}", grid, surf)):
@@ -148,7 +223,10 @@ def main():
                 lines.append(f"{tag:>22s} {name:>14s} {t_eng:10.1f} {t_copy:9.1f} {t_ref:15.1f}")
                 print(lines[-1], flush=True)
             lines.append(f"{tag:>22s} {'edges':>14s} {E:10d}")
-    lines += search_table(dev, args.iters)
+    if not args.mlp_only:
+        lines += search_table(dev, args.iters)
+    if args.mlp or args.mlp_only:
+        lines += mlp_table(dev, args.iters)
     text = "\n".join(lines) + "\n"
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
