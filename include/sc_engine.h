@@ -611,6 +611,45 @@ int sc_dsparse_backward(const sc_dsparse_desc* desc, const sc_dsparse_csr* psi_t
                         const float* z, const float* gout, float* gx, float* gw, float* gbias, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- attention kernel integral ---------------------------------------------------------------------------------------
+ * (neuralop/layers/attention_kernel_integral.py: AttentionKernelIntegral, associative form, with the rotary embedding
+ * of layers/embeddings.py RotaryEmbedding2D), on the raw outputs of the three projections in their own layout:
+ *   kn = LN(k), vn = LN(v)       per point and head over the head_dim channels (biased variance, eps 1e-5, no affine)
+ *   dots[b, h]  = sum_n (R(pos_src[b, n]) kn[b, n, h])^T vn[b, n, h]                          (head_dim x head_dim)
+ *   u[b, n, h]  = ((R(pos_qry[b, n]) q[b, n, h]) dots[b, h]) w[b, n]
+ * q, u (batch, n_qry, heads head_dim), k, v (batch, n_src, heads head_dim), dots (batch, heads, head_dim, head_dim),
+ * pos_src (batch, n_src, rotary), pos_qry (batch, n_qry, rotary), weights (batch, n_qry), all fp32 contiguous.
+ * w = 1 / n_src without weights, else weights[b, n] of the QUERY row (the reference's broadcast).  rotary = 0: R = 1 and
+ * the positions and inv_freq may be null.  rotary = 1: channel i pairs with i + head_dim / 2 and inv_freq has
+ * head_dim / 2 entries.  rotary = 2: the channels split into halves for the two coordinates, channel i of a half pairs
+ * with i + head_dim / 4, inv_freq has head_dim / 4 entries.  The angle is (coordinate rot_scale) inv_freq[i] in fp32,
+ * rot_scale = fl32(scale / min_freq) of the module; a pair (x1, x2) becomes (x1 cos - x2 sin, x2 cos + x1 sin).
+ * sc_attn_forward writes u and dots; sc_attn_backward reads dots again and recomputes everything else from q, k, v: it
+ * writes gq, gk, gv or any subset (null = not wanted; dots may be null when gq is, q, k, v, pos_src when gk and gv are).
+ * Both calls take sc_attn_workspace_bytes(desc).  Refused before any launch: a head_dim that is odd or outside 2..128,
+ * rotary = 2 with head_dim % 4, n_src, n_qry or batch n heads head_dim beyond int32, batch heads >= 65536, a null
+ * required pointer, a small workspace.  n_qry != n_src is legal here.  Neither call reads device memory on the host or
+ * waits for the device.  sc_attn_path (0 = refused): SC_ATTN_PATH_MFMA for head_dim in {32, 64, 128} (the products with
+ * the head_dim x head_dim matrices, forward and backward, on the exact-fp32 matrix instruction with points as the K
+ * dimension), SC_ATTN_PATH_VECTOR, the vector-ALU kernels, for every other even head_dim.
+ * Deterministic: no float atomics; the sums over points run in ascending order within chunks of 256 points, the chunks
+ * are added in chunk order. */
+#define SC_ATTN_PATH_VECTOR 1
+#define SC_ATTN_PATH_MFMA 2
+typedef struct {
+  int64_t batch, n_src, n_qry;
+  int32_t heads, head_dim, rotary, has_weights;
+} sc_attn_desc;
+int sc_attn_path(const sc_attn_desc* desc);
+size_t sc_attn_workspace_bytes(const sc_attn_desc* desc);
+int sc_attn_forward(const sc_attn_desc* desc, const float* q, const float* k, const float* v, const float* pos_src,
+                    const float* pos_qry, const float* inv_freq, float rot_scale, const float* weights, float* u,
+                    float* dots, void* workspace, size_t workspace_bytes, void* stream);
+int sc_attn_backward(const sc_attn_desc* desc, const float* q, const float* k, const float* v, const float* pos_src,
+                     const float* pos_qry, const float* inv_freq, float rot_scale, const float* weights,
+                     const float* dots, const float* gout, float* gq, float* gk, float* gv, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -210,6 +210,14 @@ class DsparseCsr(Structure):                                # sc_dsparse_csr
 SC_DSPARSE_PATH_GENERAL, SC_DSPARSE_PATH_MFMA = 1, 2
 
 
+class AttnDesc(Structure):                                  # sc_attn_desc
+    _fields_ = [("batch", c_int64), ("n_src", c_int64), ("n_qry", c_int64), ("heads", c_int32), ("head_dim", c_int32),
+                ("rotary", c_int32), ("has_weights", c_int32)]
+
+
+SC_ATTN_PATH_VECTOR, SC_ATTN_PATH_MFMA = 1, 2
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -277,7 +285,8 @@ class ScEngineLib:
                "sc_disco_forward_workspace_bytes", "sc_disco_forward", "sc_disco_backward", "sc_dsparse_path",
                "sc_dsparse_workspace_bytes", "sc_dsparse_forward_workspace_bytes", "sc_dsparse_forward",
                "sc_dsparse_backward", "sc_radius_grid_workspace_bytes", "sc_radius_grid_count",
-               "sc_radius_grid_fill", "sc_edge_mlp_workspace_bytes", "sc_edge_mlp_forward", "sc_edge_mlp_backward"]
+               "sc_radius_grid_fill", "sc_edge_mlp_workspace_bytes", "sc_edge_mlp_forward", "sc_edge_mlp_backward",
+               "sc_attn_path", "sc_attn_workspace_bytes", "sc_attn_forward", "sc_attn_backward"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -493,6 +502,16 @@ class ScEngineLib:
         L.sc_dsparse_backward.argtypes = [POINTER(DsparseDesc), POINTER(DsparseCsr)] + [c_void_p] * 8 + \
             [c_size_t, c_void_p]
         L.sc_dsparse_backward.restype = c_int
+        L.sc_attn_path.argtypes = [POINTER(AttnDesc)]
+        L.sc_attn_path.restype = c_int
+        L.sc_attn_workspace_bytes.argtypes = [POINTER(AttnDesc)]
+        L.sc_attn_workspace_bytes.restype = c_size_t
+        L.sc_attn_forward.argtypes = [POINTER(AttnDesc)] + [c_void_p] * 6 + [ctypes.c_float] + [c_void_p] * 4 + \
+                                     [c_size_t, c_void_p]
+        L.sc_attn_forward.restype = c_int
+        L.sc_attn_backward.argtypes = [POINTER(AttnDesc)] + [c_void_p] * 6 + [ctypes.c_float] + [c_void_p] * 7 + \
+                                      [c_size_t, c_void_p]
+        L.sc_attn_backward.restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -1067,6 +1086,37 @@ class ScEngineLib:
         self._check(self.lib.sc_dsparse_backward(byref(desc), byref(csr_t) if csr_t is not None else None, q_ptr or None,
                                                  w_ptr or None, z_ptr or None, gout_ptr or None, gx_ptr or None,
                                                  gw_ptr or None, gbias_ptr or None, ws_ptr or None, ws_bytes, stream))
+
+    @staticmethod
+    def attn_desc(*, batch, n_src, n_qry, heads, head_dim, rotary=0, has_weights=0):
+        d = AttnDesc()
+        d.batch, d.n_src, d.n_qry = int(batch), int(n_src), int(n_qry)
+        d.heads, d.head_dim, d.rotary, d.has_weights = int(heads), int(head_dim), int(rotary), int(has_weights)
+        return d
+
+    def attn_path(self, desc):
+        """the route of a descriptor: SC_ATTN_PATH_VECTOR, SC_ATTN_PATH_MFMA, or 0 where it is refused"""
+        return int(self.lib.sc_attn_path(byref(desc)))
+
+    def attn_workspace_bytes(self, desc):
+        return int(self.lib.sc_attn_workspace_bytes(byref(desc)))
+
+    def attn_forward(self, desc, q_ptr, k_ptr, v_ptr, pos_src_ptr, pos_qry_ptr, inv_freq_ptr, rot_scale, w_ptr, u_ptr,
+                     dots_ptr, ws_ptr, ws_bytes, stream=0):
+        """u = ((R q) dots) w with dots = sum_n (R LN(k))^T LN(v); u and dots are written"""
+        self._check(self.lib.sc_attn_forward(byref(desc), q_ptr or None, k_ptr or None, v_ptr or None,
+                                             pos_src_ptr or None, pos_qry_ptr or None, inv_freq_ptr or None,
+                                             float(rot_scale), w_ptr or None, u_ptr or None, dots_ptr or None,
+                                             ws_ptr or None, ws_bytes, stream))
+
+    def attn_backward(self, desc, q_ptr, k_ptr, v_ptr, pos_src_ptr, pos_qry_ptr, inv_freq_ptr, rot_scale, w_ptr,
+                      dots_ptr, gu_ptr, gq_ptr, gk_ptr, gv_ptr, ws_ptr, ws_bytes, stream=0):
+        """gq, gk and / or gv of sc_attn_forward (a zero pointer: not wanted)"""
+        self._check(self.lib.sc_attn_backward(byref(desc), q_ptr or None, k_ptr or None, v_ptr or None,
+                                              pos_src_ptr or None, pos_qry_ptr or None, inv_freq_ptr or None,
+                                              float(rot_scale), w_ptr or None, dots_ptr or None, gu_ptr or None,
+                                              gq_ptr or None, gk_ptr or None, gv_ptr or None, ws_ptr or None, ws_bytes,
+                                              stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

@@ -57,6 +57,7 @@
 #include "sc_host_fdconv.h"
 #include "sc_host_disco.h"
 #include "sc_host_disco_sparse.h"
+#include "sc_host_attn.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

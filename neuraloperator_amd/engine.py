@@ -1837,6 +1837,81 @@ class SparseDiscoFn(torch.autograd.Function):
         return (gx, gw, gb) + (None,) * 5
 
 
+class AttnIntegralFn(torch.autograd.Function):
+    """The core of AttentionKernelIntegral (associative form) as one autograd node over sc_attn_forward /
+    sc_attn_backward: u = ((R q) dots) w, dots = sum_n (R LN(k))^T LN(v).  q (B, n_qry, H D), k and v (B, n_src, H D),
+    pos_src (B, n_src, rotary), pos_qry (B, n_qry, rotary), inv_freq and weights (B, n_qry) or None, all fp32.  Saves
+    q, k, v and dots (B, H, D, D); the backward pass recomputes the norms and rotations.  No gradient reaches the
+    positions or the weights.  Neither pass waits for the device."""
+
+    @staticmethod
+    def desc(q, k, heads, rotary, has_weights):
+        return _lib.ScEngineLib.attn_desc(batch=int(k.shape[0]), n_src=int(k.shape[1]), n_qry=int(q.shape[1]),
+                                          heads=int(heads), head_dim=int(k.shape[2]) // int(heads), rotary=int(rotary),
+                                          has_weights=int(bool(has_weights)))
+
+    @staticmethod
+    def forward(ctx, q, k, v, pos_src, pos_qry, inv_freq, rot_scale, weights, heads, rotary):
+        _require_gpu(q, "q")
+        _require_gpu(k, "k")
+        opt = [t for t in (pos_src, pos_qry, inv_freq, weights) if t is not None]
+        if any(t.dtype != torch.float32 for t in [q, k, v] + opt):
+            raise ValueError(f"attn: float32 tensors, got {[t.dtype for t in [q, k, v] + opt]}")
+        if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2] \
+                or k.shape[2] % int(heads):
+            raise ValueError(f"attn: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} in {heads} heads")
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        pos_src, pos_qry, inv_freq, weights = (None if t is None else t.contiguous()
+                                               for t in (pos_src, pos_qry, inv_freq, weights))
+        if not rotary:
+            pos_src = pos_qry = inv_freq = None
+        d = AttnIntegralFn.desc(q, k, heads, rotary, weights is not None)
+        if rotary and (pos_src is None or pos_qry is None or inv_freq is None
+                       or tuple(pos_src.shape) != (d.batch, d.n_src, rotary)
+                       or tuple(pos_qry.shape) != (d.batch, d.n_qry, rotary)
+                       or inv_freq.numel() != d.head_dim // (2 * rotary)):
+            raise ValueError("attn: positions (B, n, rotary) and inv_freq of head_dim / (2 rotary) entries")
+        if weights is not None and weights.numel() != d.batch * d.n_qry:
+            raise ValueError("attn: weights hold one value per batch and query row")
+        lib = _lib.get_lib()
+        u = torch.empty_like(q)
+        dots = torch.empty((d.batch, d.heads, d.head_dim, d.head_dim), dtype=torch.float32, device=q.device)
+        p = lambda t: 0 if t is None else t.data_ptr()                                  # noqa: E731
+        with torch.cuda.device(q.device):
+            nbytes = lib.attn_workspace_bytes(d)
+            if nbytes == 0:
+                raise ValueError(f"attn: no engine route for this shape ({lib.lib.sc_last_error().decode()})")
+            ws = _ws(nbytes, q.device)
+            lib.attn_forward(d, q.data_ptr(), k.data_ptr(), v.data_ptr(), p(pos_src), p(pos_qry), p(inv_freq),
+                             rot_scale, p(weights), u.data_ptr(), dots.data_ptr(), ws.data_ptr(), nbytes,
+                             stream=_stream())
+        ctx.d, ctx.rot_scale = d, rot_scale
+        ctx.has = tuple(t is not None for t in (pos_src, pos_qry, inv_freq, weights))
+        ctx.save_for_backward(q, k, v, dots, *[t for t in (pos_src, pos_qry, inv_freq, weights) if t is not None])
+        return u
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gu):
+        q, k, v, dots, *rest = ctx.saved_tensors
+        rest = list(rest)
+        pos_src, pos_qry, inv_freq, weights = (rest.pop(0) if h else None for h in ctx.has)
+        want = ctx.needs_input_grad[:3]
+        if not any(want):
+            return (None,) * 10
+        gu = gu.float().contiguous()
+        gq, gk, gv = (torch.empty_like(t) if w else None for t, w in zip((q, k, v), want))
+        lib = _lib.get_lib()
+        p = lambda t: 0 if t is None else t.data_ptr()                                  # noqa: E731
+        with torch.cuda.device(gu.device):
+            nbytes = lib.attn_workspace_bytes(ctx.d)
+            ws = _ws(nbytes, gu.device)
+            lib.attn_backward(ctx.d, q.data_ptr(), k.data_ptr(), v.data_ptr(), p(pos_src), p(pos_qry), p(inv_freq),
+                              ctx.rot_scale, p(weights), dots.data_ptr(), gu.data_ptr(), p(gq), p(gk), p(gv),
+                              ws.data_ptr(), nbytes, stream=_stream())
+        return (gq, gk, gv) + (None,) * 7
+
+
 class EngineRawOps:
     """The local stages of a spectral layer and their adjoints as plain calls (no autograd): what a hand-scheduled
     pipeline (mpu.ModeParallelSpectralConv: transform chunk j+1 while chunk j is on the wire) is built from.
