@@ -650,6 +650,52 @@ int sc_attn_backward(const sc_attn_desc* desc, const float* q, const float* k, c
                      const float* dots, const float* gout, float* gq, float* gk, float* gv, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- finite differences on a point cloud -----------------------------------------------------------------------------
+ * (neuralop/losses/differentiation.py:728-855, get_non_uniform_fd_weights / non_uniform_fd.)  All arrays contiguous,
+ * coordinates, weights and values fp32, indices and splits int64.  None of the four calls needs a workspace, reads
+ * device memory on the host or waits for the device; no float atomics, every sum runs in a fixed order.
+ *
+ * sc_knn: the k nearest data points (n, d) of every query (m, d), d = 1..3, 3 <= k <= min(32, n), by brute force:
+ * index[m, k] and d2[m, k] in ascending (d2, data index), d2 = sum_i (q_i - p_i)^2 in fp32 in dimension order (the
+ * expression of sc_radius_count; a NaN counts as +inf).  The order is total: two launches give the same bits.
+ *
+ * sc_nufd_weights: per point the minimum-norm solution of A w = e_{deriv + 1}, which is what the reference's lstsq
+ * returns: row 0 of the (d + 1) x k matrix A is ones, row i + 1 the differences of coordinate i to the point's own,
+ * the columns of masked neighbours are zero.  A neighbour is masked where has_radius and d2 > (float)(radius radius)
+ * (formed in double), except the first three, and where its index lies outside [0, n).  w = A^T (A A^T + lambda I)^-1 e,
+ * formed and solved by Cholesky in float64 and rounded to fp32 into weights[n, n_deriv, k]; lambda = 0, or 1e-6 for the
+ * reference's regularize_lstsq (the same w as its (A^T A + lambda I) w = A^T e).  A point whose Cholesky meets a pivot
+ * that is not above 2^-40 trace(A A^T + lambda I) -- collinear or coincident neighbours -- is ill-posed: all its weights
+ * are 0 and flag[n] is 1 (0 elsewhere); the reference returns an rcond-dependent truncated solution there.
+ *
+ * sc_nufd_apply:         out[j, b, p] = sum_m weights[p, j, m] values[b, index[p, m]]        values (batch, n)
+ * sc_nufd_apply_adjoint: gvalues[b, q] = sum_{(p, m): index[p, m] = q} sum_j weights[p, j, m] gout[j, b, p]
+ * both in fp32 with fmaf, the first in neighbour order, the second over col_splits / perm of sc_csr_transpose of the
+ * stencil (rows = cols = n, row_splits = k arange(n + 1)) in ascending entry id.  Every index read from an array is
+ * range-checked on the device before it addresses memory.
+ * Refused before any launch: d outside 1..3, k outside 3..32 (knn), k > n (knn), k < d + 1 (weights), more than 8
+ * derivatives or one outside [0, d), a radius with d = 3 (the three neighbours always kept are fewer than d + 1), a
+ * negative radius or lambda, batch outside 1..65535, counts beyond int32, null pointers.  n = 0 (m = 0) launches
+ * nothing.  sc_nufd_apply and its adjoint read n, k, n_deriv and batch of the descriptor only. */
+typedef struct {
+  int32_t d, k;
+  int64_t n, m;
+} sc_knn_desc;
+typedef struct {
+  int64_t n;
+  int32_t d, k, n_deriv, batch;
+  int32_t deriv[8];
+  int32_t has_radius, reserved;
+  double radius, lambda;
+} sc_nufd_desc;
+int sc_knn(const sc_knn_desc* desc, const float* data, const float* queries, int64_t* index, float* d2, void* stream);
+int sc_nufd_weights(const sc_nufd_desc* desc, const float* points, const int64_t* index, const float* d2,
+                    float* weights, int32_t* flag, void* stream);
+int sc_nufd_apply(const sc_nufd_desc* desc, const float* weights, const int64_t* index, const float* values, float* out,
+                  void* stream);
+int sc_nufd_apply_adjoint(const sc_nufd_desc* desc, const float* weights, const int64_t* col_splits,
+                          const int32_t* perm, const float* gout, float* gvalues, void* stream);
+
 /* gbias[c] = sum_b Re(ghat[b, c, dc]) -- the bias gradient read off the DC coefficient of
  * the already-computed SC_FWD_ADJ_C2R spectrum (autograd of :567-568). */
 int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t channels,

@@ -10,7 +10,8 @@ from .optim import AdamW  # noqa: F401
 from .galore import TensorGaLoreProjector  # noqa: F401
 from .spherical import SHT, SphericalConv  # noqa: F401
 from .harmonics import InverseRealSHT, RealSHT, install_torch_harmonics  # noqa: F401
-from .differentiation import FiniteDiff, FourierDiff  # noqa: F401
+from .differentiation import (FiniteDiff, FourierDiff, NonUniformFD, get_non_uniform_fd_weights,  # noqa: F401
+                              non_uniform_fd)
 from .losses import H1Loss, LpLoss  # noqa: F401
 from .gno import GNOBlock, IntegralTransform, NeighborSearch, segment_csr  # noqa: F401
 from .differential_conv import FiniteDifferenceConvolution  # noqa: F401

@@ -218,6 +218,16 @@ class AttnDesc(Structure):                                  # sc_attn_desc
 SC_ATTN_PATH_VECTOR, SC_ATTN_PATH_MFMA = 1, 2
 
 
+class KnnDesc(Structure):                                   # sc_knn_desc
+    _fields_ = [("d", c_int32), ("k", c_int32), ("n", c_int64), ("m", c_int64)]
+
+
+class NufdDesc(Structure):                                  # sc_nufd_desc
+    _fields_ = [("n", c_int64), ("d", c_int32), ("k", c_int32), ("n_deriv", c_int32), ("batch", c_int32),
+                ("deriv", c_int32 * 8), ("has_radius", c_int32), ("reserved", c_int32), ("radius", ctypes.c_double),
+                ("lam", ctypes.c_double)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -286,7 +296,8 @@ class ScEngineLib:
                "sc_dsparse_workspace_bytes", "sc_dsparse_forward_workspace_bytes", "sc_dsparse_forward",
                "sc_dsparse_backward", "sc_radius_grid_workspace_bytes", "sc_radius_grid_count",
                "sc_radius_grid_fill", "sc_edge_mlp_workspace_bytes", "sc_edge_mlp_forward", "sc_edge_mlp_backward",
-               "sc_attn_path", "sc_attn_workspace_bytes", "sc_attn_forward", "sc_attn_backward"]
+               "sc_attn_path", "sc_attn_workspace_bytes", "sc_attn_forward", "sc_attn_backward", "sc_knn",
+               "sc_nufd_weights", "sc_nufd_apply", "sc_nufd_apply_adjoint"]
 
     def __init__(self, path=DEFAULT_LIB):
         if not os.path.isfile(path):
@@ -512,6 +523,12 @@ class ScEngineLib:
         L.sc_attn_backward.argtypes = [POINTER(AttnDesc)] + [c_void_p] * 6 + [ctypes.c_float] + [c_void_p] * 7 + \
                                       [c_size_t, c_void_p]
         L.sc_attn_backward.restype = c_int
+        L.sc_knn.argtypes = [POINTER(KnnDesc)] + [c_void_p] * 5
+        L.sc_nufd_weights.argtypes = [POINTER(NufdDesc)] + [c_void_p] * 6
+        L.sc_nufd_apply.argtypes = [POINTER(NufdDesc)] + [c_void_p] * 5
+        L.sc_nufd_apply_adjoint.argtypes = [POINTER(NufdDesc)] + [c_void_p] * 6
+        for s in ("sc_knn", "sc_nufd_weights", "sc_nufd_apply", "sc_nufd_apply_adjoint"):
+            getattr(L, s).restype = c_int
         for s in ("sc_wire_pack_c32", "sc_wire_unpack_c32"):
             getattr(L, s).argtypes = [c_void_p, c_void_p] + [c_int64] * 7 + [c_void_p]
             getattr(L, s).restype = c_int
@@ -1117,6 +1134,41 @@ class ScEngineLib:
                                               float(rot_scale), w_ptr or None, dots_ptr or None, gu_ptr or None,
                                               gq_ptr or None, gk_ptr or None, gv_ptr or None, ws_ptr or None, ws_bytes,
                                               stream))
+
+    @staticmethod
+    def knn_desc(d, n, m, k):
+        r = KnnDesc()
+        r.d, r.k, r.n, r.m = int(d), int(k), int(n), int(m)
+        return r
+
+    def knn(self, desc, data_ptr, queries_ptr, index_ptr, d2_ptr, stream=0):
+        """index[m, k] and d2[m, k] of every query's k nearest data points, ascending (d2, data index) (sc_knn)"""
+        self._check(self.lib.sc_knn(byref(desc), data_ptr or None, queries_ptr or None, index_ptr or None,
+                                    d2_ptr or None, stream))
+
+    @staticmethod
+    def nufd_desc(*, n, k, n_deriv=1, batch=1, d=1, deriv=(), radius=None, lam=0.0):
+        r = NufdDesc()
+        r.n, r.d, r.k, r.n_deriv, r.batch = int(n), int(d), int(k), int(n_deriv), int(batch)
+        for i, v in enumerate(list(deriv)[:8]):
+            r.deriv[i] = int(v)
+        r.has_radius, r.radius, r.lam = int(radius is not None), float(radius or 0.0), float(lam)
+        return r
+
+    def nufd_weights(self, desc, points_ptr, index_ptr, d2_ptr, weights_ptr, flag_ptr, stream=0):
+        """weights[n, n_deriv, k] of the point-cloud finite differences and flag[n] of the ill-posed points"""
+        self._check(self.lib.sc_nufd_weights(byref(desc), points_ptr or None, index_ptr or None, d2_ptr or None,
+                                             weights_ptr or None, flag_ptr or None, stream))
+
+    def nufd_apply(self, desc, weights_ptr, index_ptr, values_ptr, out_ptr, stream=0):
+        """out[j, b, p] = sum_m weights[p, j, m] values[b, index[p, m]]"""
+        self._check(self.lib.sc_nufd_apply(byref(desc), weights_ptr or None, index_ptr or None, values_ptr or None,
+                                           out_ptr or None, stream))
+
+    def nufd_apply_adjoint(self, desc, weights_ptr, col_splits_ptr, perm_ptr, gout_ptr, gvalues_ptr, stream=0):
+        """gvalues[b, q] = sum over the stencil entries that name q (sc_csr_transpose order) of w gout"""
+        self._check(self.lib.sc_nufd_apply_adjoint(byref(desc), weights_ptr or None, col_splits_ptr or None,
+                                                   perm_ptr or None, gout_ptr or None, gvalues_ptr or None, stream))
 
     def modegemm_msum(self, a_ptr, b_ptr, c_ptr, stream=0, **kw):
         self._check(self.lib.sc_modegemm_msum(byref(self._gemm_desc(kw)), a_ptr, b_ptr, c_ptr, stream))

@@ -58,6 +58,7 @@
 #include "sc_host_disco.h"
 #include "sc_host_disco_sparse.h"
 #include "sc_host_attn.h"
+#include "sc_host_nufd.h"
 
 // ------------------------------------------------------------------------------------------
 // plan

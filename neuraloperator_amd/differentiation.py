@@ -35,13 +35,28 @@ engine holds D, D^T (orders 1 and 2) of every axis as 7-band tables built in flo
 every method is ONE ``sc_band_apply`` launch; ``laplacian`` / ``divergence`` / ``curl`` sum inside the kernel.  The
 backward pass is the same launch with the transposed tables and the term list transposed, so it differentiates any
 number of times.  One difference: a non-periodic axis shorter than 4 points raises ``ValueError`` (the reference's
-boundary stencils die there with an ``IndexError``).  ``central_diff_*`` and ``non_uniform_fd`` are not provided."""
+boundary stencils die there with an ``IndexError``).  ``central_diff_*`` are not provided.
+
+``get_non_uniform_fd_weights`` / ``non_uniform_fd`` (the reference's :728-855) and the class ``NonUniformFD`` are
+first derivatives on a point cloud.  The reference forms ``cdist(points, points)`` (N x N), takes ``topk`` and calls
+``lstsq`` on every point's (d + 1) x k system ``A w = e``; what ``lstsq`` returns there is the minimum-norm solution
+``w = A^T (A A^T)^-1 e``, and its regularised form ``(A^T A + 1e-6 I) w = A^T e`` is ``A^T (A A^T + 1e-6 I)^-1 e``.  On
+the engine (sc_kernels_nufd.h) that is a brute-force k-nearest-neighbour search over LDS tiles, one (d + 1) x (d + 1)
+Cholesky solve per point in float64, and a gather-dot whose adjoint gathers over the transposed stencil: O(N k) memory,
+the stencil built once per point set by ``NonUniformFD``.  Differences to the reference: neighbours at exactly equal
+distance come in ascending index (``topk`` leaves their order open); a point whose system is singular -- collinear or
+coincident neighbours -- gets all-zero weights and is listed by ``NonUniformFD.ill_posed()`` (``lstsq`` returns an
+rcond-dependent truncated solution there); the solve runs in float64 whatever ``lstsq`` does in fp32.  The engine takes
+fp32 device tensors, points (N, d) with d = 1..3 that need no gradient, d + 1 <= k <= 32 after the clamp, at most 8
+derivative indices in [0, d), and a radius only with d <= 2; every other call -- CPU tensors, float64, d > 3, k > 32,
+gradients with respect to the points -- runs the reference's formula in torch."""
+import contextlib
 import math
 
 import numpy as np
 import torch
 
-from . import engine
+from . import blocks, engine
 
 _AXES = "xyz"
 
@@ -357,3 +372,167 @@ class FiniteDiff:
                  (1, 2, 1.0, 0, 1), (0, 2, -1.0, 1, 1)]        # dv/dx - du/dy
         y, lead, spatial = self._apply(u, 3, terms, 3, False)
         return y.reshape(*lead, 3, *spatial)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# finite differences on a point cloud
+# ---------------------------------------------------------------------------------------------------------------------
+ROUTES = ("auto", "engine", "torch")
+_ROUTE = "auto"
+
+
+@contextlib.contextmanager
+def route(name):
+    """Inside the block the point-cloud finite differences take this route: "engine" (ValueError at a call that is not
+    eligible), "torch" (the reference's formula) or "auto" (the engine wherever the call is eligible)."""
+    global _ROUTE
+    if name not in ROUTES:
+        raise ValueError(f"non_uniform_fd: route must be one of {ROUTES}, got {name!r}")
+    saved, _ROUTE = _ROUTE, name
+    try:
+        yield
+    finally:
+        _ROUTE = saved
+
+
+def _nufd_k(points, num_neighbors):
+    return min(max(num_neighbors, 3), points.shape[0])
+
+
+def on_engine(points, values=None, num_neighbors=5, derivative_indices=[0], radius=None, regularize_lstsq=False):
+    """True where get_non_uniform_fd_weights / non_uniform_fd / NonUniformFD with these arguments run the engine's
+    kernels (module docstring); ``values`` may be left out."""
+    if _ROUTE == "torch" or not torch.is_tensor(points) or points.dim() != 2:
+        return False
+    tensors = [points] + ([] if values is None else [values])
+    if any(t.dtype != torch.float32 for t in tensors) or not all(blocks._on_engine(t) for t in tensors):
+        return False
+    n, d = int(points.shape[0]), int(points.shape[1])
+    if not 1 <= d <= 3 or points.requires_grad:
+        return False
+    if not isinstance(num_neighbors, int) or isinstance(num_neighbors, bool):
+        return False
+    k = _nufd_k(points, num_neighbors)
+    try:
+        deriv = [int(i) for i in derivative_indices]
+    except (TypeError, ValueError):
+        return False
+    if not d + 1 <= k <= engine.NUFD_MAX_K or not 1 <= len(deriv) <= engine.NUFD_MAX_DERIV:
+        return False
+    if any(not 0 <= i < d for i in deriv) or (radius is not None and d > 2):
+        return False
+    if values is not None and (values.dim() < 1 or values.shape[-1] != n):
+        return False
+    return True
+
+
+def _take_engine(what, *args):
+    if on_engine(*args):
+        return True
+    if _ROUTE == "engine":
+        raise ValueError(f"{what}: route 'engine', but this call is not eligible for the engine (see on_engine)")
+    return False
+
+
+def _weights_torch(points, num_neighbors, derivative_indices, radius, regularize_lstsq):
+    """the reference's chain of torch calls (:756-812): dense distances, topk, lstsq"""
+    n, d = points.shape
+    k = _nufd_k(points, num_neighbors)
+    nd = len(derivative_indices)
+    dist, indices = torch.topk(torch.cdist(points, points, p=2), k=k, dim=1, largest=False)
+    keep = torch.ones_like(dist, dtype=torch.bool)
+    if radius is not None:
+        keep = dist <= radius
+        keep[:, :3] = True
+    A = torch.ones((n, d + 1, k), dtype=points.dtype, device=points.device)
+    for i in range(d):
+        A[:, i + 1, :] = points[indices, i] - points[:, i].unsqueeze(1)
+    A = A.unsqueeze(1).expand(-1, nd, -1, -1) * keep.unsqueeze(1).unsqueeze(2)
+    b = torch.zeros((nd, d + 1, 1), dtype=points.dtype, device=points.device)
+    for j, i in enumerate(derivative_indices):
+        b[j, i + 1] = 1
+    b = b.unsqueeze(0).expand(n, -1, -1, -1)
+    if regularize_lstsq:
+        At = A.transpose(-2, -1)
+        gram = torch.matmul(At, A) + engine.NUFD_LAMBDA * torch.eye(k, dtype=A.dtype, device=A.device)
+        w = torch.cholesky_solve(torch.matmul(At, b), torch.linalg.cholesky(gram)).squeeze(-1)
+    else:
+        w = torch.linalg.lstsq(A, b).solution
+    return indices, w.squeeze(-1)
+
+
+def get_non_uniform_fd_weights(points, num_neighbors=5, derivative_indices=[0], radius=None, regularize_lstsq=False):
+    """Finite-difference weights of the first derivatives on a point cloud, as the reference's function: points (N, d),
+    ``k = min(max(num_neighbors, 3), N)`` nearest neighbours per point (itself included), ``derivative_indices`` the
+    coordinates to differentiate along, ``radius`` zeroes the weights of farther neighbours (the first three are always
+    kept), ``regularize_lstsq`` adds 1e-6 to the normal equations.  Returns ``indices`` int64 (N, k) and ``fd_weights``
+    (N, len(derivative_indices), k)."""
+    if not _take_engine("get_non_uniform_fd_weights", points, None, num_neighbors, derivative_indices, radius,
+                        regularize_lstsq):
+        return _weights_torch(points, num_neighbors, derivative_indices, radius, regularize_lstsq)
+    st = engine.NufdStencil(points, _nufd_k(points, num_neighbors), derivative_indices, radius, regularize_lstsq)
+    return st.indices, st.fd_weights
+
+
+def non_uniform_fd(points, values, num_neighbors=5, derivative_indices=[0], radius=None, regularize_lstsq=False):
+    """First derivatives of ``values`` (N,) on the point cloud ``points`` (N, d): (len(derivative_indices), N).  Builds
+    the stencil on every call, as the reference does; ``NonUniformFD`` builds it once."""
+    if not _take_engine("non_uniform_fd", points, values, num_neighbors, derivative_indices, radius, regularize_lstsq):
+        indices, w = _weights_torch(points, num_neighbors, derivative_indices, radius, regularize_lstsq)
+        return torch.einsum("nij,nj->in", w, values[indices])
+    if values.dim() != 1:
+        raise ValueError(f"non_uniform_fd: values must be (N,), got {tuple(values.shape)}; NonUniformFD takes (..., N)")
+    st = engine.NufdStencil(points, _nufd_k(points, num_neighbors), derivative_indices, radius, regularize_lstsq)
+    return engine.NufdApplyFn.apply(values.reshape(1, -1), st)[:, 0]
+
+
+class NonUniformFD:
+    """First derivatives on a fixed point cloud: the stencil -- neighbour indices, weights and, on the engine, its
+    transpose for the backward pass -- is built once, ``fd(values)`` applies it to ``values`` (..., N) and returns
+    (n_deriv, ..., N), differentiable with respect to ``values`` through one autograd node (engine.NufdApplyFn).
+    Parameters as ``get_non_uniform_fd_weights``.  Attributes: ``indices`` (N, k), ``fd_weights`` (N, n_deriv, k),
+    ``k``.  On the engine neither the call nor its backward pass waits for the device, so a step replays from a captured
+    graph; ``ill_posed()`` is the one call that does."""
+
+    _MAX_BATCH = 65535
+
+    def __init__(self, points, num_neighbors=5, derivative_indices=[0], radius=None, regularize_lstsq=False):
+        self.derivative_indices = [int(i) for i in derivative_indices]
+        self.k = _nufd_k(points, num_neighbors)
+        self.n = int(points.shape[0])
+        self._stencil = None
+        if _take_engine("NonUniformFD", points, None, num_neighbors, derivative_indices, radius, regularize_lstsq):
+            self._stencil = engine.NufdStencil(points, self.k, self.derivative_indices, radius, regularize_lstsq)
+            self.indices, self.fd_weights = self._stencil.indices, self._stencil.fd_weights
+        else:
+            self.indices, self.fd_weights = _weights_torch(points, num_neighbors, self.derivative_indices, radius,
+                                                           regularize_lstsq)
+
+    def on_engine(self, values=None):
+        """True where ``self(values)`` runs the engine's kernels"""
+        if self._stencil is None or _ROUTE == "torch":
+            return False
+        return values is None or (values.dtype == torch.float32 and blocks._on_engine(values) and values.dim() >= 1
+                                  and values.shape[-1] == self.n and values.device == self._stencil.device)
+
+    def ill_posed(self):
+        """indices of the points whose system was singular (all-zero weights); waits for the device.  The torch route
+        flags nothing."""
+        if self._stencil is None:
+            return torch.empty(0, dtype=torch.int64, device=self.indices.device)
+        return torch.nonzero(self._stencil.flag, as_tuple=False).reshape(-1)
+
+    def __call__(self, values):
+        if values.dim() < 1 or values.shape[-1] != self.n:
+            raise ValueError(f"NonUniformFD: values must be (..., {self.n}), got {tuple(values.shape)}")
+        if not self.on_engine(values):
+            if _ROUTE == "engine":
+                raise ValueError("NonUniformFD: route 'engine', but this call is not eligible for the engine "
+                                 "(see on_engine)")
+            return torch.einsum("nij,...nj->i...n", self.fd_weights.to(values.dtype), values[..., self.indices])
+        lead = tuple(values.shape[:-1])
+        flat = values.reshape(-1, self.n)
+        parts = [engine.NufdApplyFn.apply(flat[i:i + self._MAX_BATCH], self._stencil)
+                 for i in range(0, max(flat.shape[0], 1), self._MAX_BATCH)]
+        out = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return out.reshape(len(self.derivative_indices), *lead, self.n)

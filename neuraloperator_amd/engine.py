@@ -1912,6 +1912,104 @@ class AttnIntegralFn(torch.autograd.Function):
         return (gq, gk, gv) + (None,) * 7
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# finite differences on a point cloud (sc_kernels_nufd.h): k nearest neighbours, weights per point, apply and adjoint
+# ---------------------------------------------------------------------------------------------------------------------
+NUFD_MAX_K, NUFD_MAX_DERIV, NUFD_LAMBDA = 32, 8, 1e-6
+
+
+def knn_search(data, queries, k):
+    """The k nearest data points (n, d) of every query (m, d), d = 1..3, 3 <= k <= min(32, n): index int64 (m, k) and
+    squared distances fp32 (m, k) in ascending (d2, data index).  Brute force over LDS tiles; nothing is m x n in
+    memory and nothing waits for the device."""
+    data = _gno_tensor(data.detach(), "data")
+    queries = _gno_tensor(queries.detach(), "queries", device=data.device)
+    if data.dim() != 2 or queries.dim() != 2 or data.shape[1] != queries.shape[1] or not 1 <= data.shape[1] <= 3:
+        raise ValueError(f"knn: data {tuple(data.shape)} and queries {tuple(queries.shape)} must be (n, d) and (m, d) "
+                         "with d = 1, 2 or 3")
+    n, m, dev = int(data.shape[0]), int(queries.shape[0]), data.device
+    if not 3 <= int(k) <= min(NUFD_MAX_K, n):
+        raise ValueError(f"knn: k = {k} outside 3 .. min({NUFD_MAX_K}, {n} data points)")
+    lib = _lib.get_lib()
+    index = torch.empty((m, int(k)), dtype=torch.int64, device=dev)
+    d2 = torch.empty((m, int(k)), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.knn(lib.knn_desc(data.shape[1], n, m, k), data.data_ptr(), queries.data_ptr(), index.data_ptr(),
+                d2.data_ptr(), stream=_stream())
+    return index, d2
+
+
+class NufdStencil:
+    """The finite-difference stencil of a point cloud, built once: ``indices`` int64 (N, k), ``d2`` fp32 (N, k),
+    ``fd_weights`` fp32 (N, n_deriv, k), ``flag`` int32 (N) (1 = ill-posed point, all its weights 0) and the transpose
+    of the stencil (col_splits, perm) the adjoint gathers over.  points (N, d) fp32 on the device, d = 1..3,
+    d + 1 <= k <= 32, derivative indices in [0, d), a radius only with d <= 2.  Nothing here waits for the device."""
+
+    def __init__(self, points, k, derivative_indices, radius=None, regularize=False):
+        points = _gno_tensor(points.detach(), "points")
+        if points.dim() != 2 or not 1 <= points.shape[1] <= 3:
+            raise ValueError(f"nufd: points {tuple(points.shape)} must be (N, d) with d = 1, 2 or 3")
+        n, d, dev = int(points.shape[0]), int(points.shape[1]), points.device
+        deriv = [int(i) for i in derivative_indices]
+        if not max(3, d + 1) <= int(k) <= min(NUFD_MAX_K, n):
+            raise ValueError(f"nufd: k = {k} outside max(3, d + 1) .. min({NUFD_MAX_K}, N = {n})")
+        if not 1 <= len(deriv) <= NUFD_MAX_DERIV or any(not 0 <= i < d for i in deriv):
+            raise ValueError(f"nufd: 1 to {NUFD_MAX_DERIV} derivative indices in [0, {d}), got {deriv}")
+        if radius is not None and d > 2:
+            raise ValueError("nufd: a radius needs d <= 2")
+        self.n, self.d, self.k, self.n_deriv, self.device = n, d, int(k), len(deriv), dev
+        lib = _lib.get_lib()
+        self.indices, self.d2 = knn_search(points, points, self.k)
+        self.fd_weights = torch.empty((n, self.n_deriv, self.k), dtype=torch.float32, device=dev)
+        self.flag = torch.empty(n, dtype=torch.int32, device=dev)
+        desc = lib.nufd_desc(n=n, k=self.k, n_deriv=self.n_deriv, d=d, deriv=deriv, radius=radius,
+                             lam=NUFD_LAMBDA if regularize else 0.0)
+        with torch.cuda.device(dev):
+            lib.nufd_weights(desc, points.data_ptr(), self.indices.data_ptr(), self.d2.data_ptr(),
+                             self.fd_weights.data_ptr(), self.flag.data_ptr(), stream=_stream())
+        splits = torch.arange(n + 1, dtype=torch.int64, device=dev) * self.k
+        self.col_splits, self.perm, _ = CsrGraph(splits, self.indices.reshape(-1), n).transpose()
+
+    def desc(self, batch):
+        return _lib.ScEngineLib.nufd_desc(n=self.n, k=self.k, n_deriv=self.n_deriv, batch=batch)
+
+
+class NufdApplyFn(torch.autograd.Function):
+    """out[j, b, p] = sum_m fd_weights[p, j, m] values[b, indices[p, m]] (sc_nufd_apply) for values (B, N) fp32 and a
+    NufdStencil; the backward pass is one sc_nufd_apply_adjoint, a gather over the stencil's transpose in a fixed order.
+    Neither pass waits for the device."""
+
+    @staticmethod
+    def forward(ctx, values, stencil):
+        _require_gpu(values, "values")
+        if values.dtype != torch.float32 or values.dim() != 2 or values.shape[1] != stencil.n:
+            raise ValueError(f"nufd: values must be float32 (B, {stencil.n}), got {values.dtype} {tuple(values.shape)}")
+        if values.device != stencil.device:
+            raise ValueError(f"nufd: values on {values.device}, the stencil on {stencil.device}")
+        values = values.contiguous()
+        batch = int(values.shape[0])
+        out = torch.empty((stencil.n_deriv, batch, stencil.n), dtype=torch.float32, device=values.device)
+        if batch and stencil.n:
+            with torch.cuda.device(values.device):
+                _lib.get_lib().nufd_apply(stencil.desc(batch), stencil.fd_weights.data_ptr(), stencil.indices.data_ptr(),
+                                          values.data_ptr(), out.data_ptr(), stream=_stream())
+        ctx.stencil = stencil
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        st = ctx.stencil
+        gout = gout.float().contiguous()
+        batch = int(gout.shape[1])
+        gv = torch.empty((batch, st.n), dtype=torch.float32, device=gout.device)
+        if batch and st.n:
+            with torch.cuda.device(gout.device):
+                _lib.get_lib().nufd_apply_adjoint(st.desc(batch), st.fd_weights.data_ptr(), st.col_splits.data_ptr(),
+                                                  st.perm.data_ptr(), gout.data_ptr(), gv.data_ptr(), stream=_stream())
+        return gv, None
+
+
 class EngineRawOps:
     """The local stages of a spectral layer and their adjoints as plain calls (no autograd): what a hand-scheduled
     pipeline (mpu.ModeParallelSpectralConv: transform chunk j+1 while chunk j is on the wire) is built from.
