@@ -100,3 +100,137 @@ def _load(modname, path):
     sys.modules[modname] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+# ---- free-standing calls of sc_kernels_sht.h through the C-ABI ----------------------------------------------------------
+# The emulation tier (tests/test_emu_sht.py) and the GPU tier (tests/test_gpu_sht_kernels.py, device="cuda:0") run the same
+# runner against the same float64 einsum with the same fp32 table.
+from fdconv_reference import U, gamma, worst_ratio  # noqa: E402,F401
+
+SHT_LT, SHT_ROWS, SHT_PB, SHT_QU = 4, 16, 4, 8          # lines per lane, rows per workgroup / wave, terms per step
+
+
+def crandn(g, *shape):
+    return torch.complex(torch.randn(*shape, generator=g), torch.randn(*shape, generator=g))
+
+
+def kernel_tables(nlat, lmax, mmax, kind, seed=0):
+    """(analysis, synthesis) fp32 (lmax, nlat, mmax), m fastest.  kind "real": f64_tables on the Legendre-Gauss grid,
+    rounded once; "random": normal entries with the triangle l < m set to exactly zero (the kernels skip it)"""
+    if kind == "real":
+        a, s = f64_tables(nlat, lmax, mmax, "legendre-gauss", "ortho")
+        return tuple(t.permute(1, 2, 0).contiguous().float() for t in (a, s))
+    g = torch.Generator().manual_seed(seed)
+    keep = (torch.arange(lmax)[:, None, None] >= torch.arange(mmax)[None, None, :]).float()
+    return tuple((torch.randn(lmax, nlat, mmax, generator=g) * keep).contiguous() for _ in range(2))
+
+
+def run_legendre(lib, which, src, tab, device="cpu", stream=0):
+    """sc_legendre_analysis / _synthesis: src (lines, Q, mmax) complex64, tab (lmax, nlat, mmax) fp32 -> (lines, P, mmax)
+    on the host, every element pre-set to NaN"""
+    lines, _, mmax = (int(v) for v in src.shape)
+    lmax, nlat = int(tab.shape[0]), int(tab.shape[1])
+    rows = lmax if which == "analysis" else nlat
+    s, t = src.contiguous().to(device), tab.contiguous().to(device)
+    out = torch.full((lines, rows, mmax, 2), float("nan"), device=device)
+    getattr(lib, "legendre_" + which)(torch.view_as_real(s).data_ptr(), t.data_ptr(), out.data_ptr(), lines, nlat, lmax,
+                                      mmax, stream)
+    return torch.view_as_complex(out.cpu())
+
+
+def want_legendre(which, src, tab, absolute=False):
+    """float64 contraction as (lines, P, mmax, 2) real / imaginary parts; absolute: of the absolute values (the A of the
+    bound: the table is real, so either part is its own sum of products)"""
+    s = torch.view_as_real(src.contiguous()).numpy().astype(np.float64)
+    t = tab.numpy().astype(np.float64)
+    if absolute:
+        s, t = np.abs(s), np.abs(t)
+    return np.einsum("nkmc,lkm->nlmc" if which == "analysis" else "nlmc,lkm->nkmc", s, t)
+
+
+def legendre_roundings(which, nlat, lmax):
+    """N of k_legendre_*: one product and one sum per term of the contracted axis (one fmaf where the compiler fuses
+    them), Q terms in index order; the padding terms past Q add an exact 0: Q + 1"""
+    return (nlat if which == "analysis" else lmax) + 1
+
+
+# name -> (lines, nlat, lmax, mmax, table kind): a small covering set of lines 1, 3, 4, 5; output rows 1, 3, 4, 5, 15, 16,
+# 17, 33; summed extents 1, 7, 8, 9, 17 (analysis sums nlat into lmax rows, synthesis lmax into nlat rows); mmax 1, 63,
+# 64, 65, 129 on either side of lmax
+def _sht_cases():
+    c = {}
+    for lines, nlat, lmax, mmax in ((1, 1, 1, 1), (3, 7, 3, 63), (4, 8, 4, 64), (5, 9, 5, 65), (1, 17, 15, 129),
+                                    (3, 15, 17, 1), (4, 16, 8, 5), (5, 33, 7, 3), (1, 4, 9, 65), (3, 5, 16, 9),
+                                    (4, 3, 33, 17), (5, 1, 17, 64), (3, 17, 33, 63)):
+        c[f"a_L{lines}_{nlat}x{lmax}x{mmax}_random"] = (lines, nlat, lmax, mmax, "random")
+    for lines, nlat, lmax, mmax in ((3, 7, 3, 63), (5, 9, 5, 65), (1, 17, 15, 129), (4, 16, 8, 5), (3, 17, 33, 63)):
+        c[f"a_L{lines}_{nlat}x{lmax}x{mmax}_real"] = (lines, nlat, lmax, mmax, "real")
+    for lmax in (64, 65, 71, 72, 73):                    # b: the synthesis sum of the second 64-column group starts at 64
+        c[f"b_L2_5x{lmax}x65_random"] = (2, 5, lmax, 65, "random")
+    for lmax in (64, 72, 130):                           # .. and of the third group at 128
+        c[f"b_L2_5x{lmax}x129_random"] = (2, 5, lmax, 129, "random")
+    c["b_L5_9x73x65_real"] = (5, 9, 73, 65, "real")
+    return c
+
+
+SHT_KERNEL_CASES = _sht_cases()
+EMU_SHT_KERNEL_CASES = ("a_L1_1x1x1_random", "a_L5_9x5x65_random", "a_L3_5x16x9_random", "a_L4_3x33x17_random",
+                        "a_L4_16x8x5_real", "b_L2_5x64x65_random", "b_L2_5x71x65_random", "b_L2_5x73x65_random",
+                        "b_L2_5x72x129_random", "b_L2_5x130x129_random")
+ADJOINT_CASES = ("a_L5_9x5x65_random", "a_L3_17x33x63_real", "b_L2_5x130x129_random")
+
+
+def sht_case_inputs(name, seed):
+    """(x (lines, nlat, mmax), c (lines, lmax, mmax), analysis table, synthesis table)"""
+    lines, nlat, lmax, mmax, kind = SHT_KERNEL_CASES[name]
+    g = torch.Generator().manual_seed(seed)
+    ta, ts = kernel_tables(nlat, lmax, mmax, kind, seed)
+    return crandn(g, lines, nlat, mmax), crandn(g, lines, lmax, mmax), ta, ts
+
+
+def run_sht_case(lib, inputs, device="cpu", stream=0):
+    """(analysis of x with the analysis table, synthesis of c with the synthesis table)"""
+    x, c, ta, ts = inputs
+    return run_legendre(lib, "analysis", x, ta, device, stream), run_legendre(lib, "synthesis", c, ts, device, stream)
+
+
+def check_sht_case(name, inputs, got):
+    """the two bars of both kernels and their exact zeros; prints and returns the worst ratio"""
+    x, c, ta, ts = inputs
+    lmax, nlat, mmax = (int(v) for v in ta.shape)
+    below = torch.arange(lmax)[:, None, None] < torch.arange(mmax)[None, None, :]
+    assert not (ta[below.expand_as(ta)].any() or ts[below.expand_as(ts)].any())   # the triangle the kernels skip
+    worst = 0.0
+    for which, src, tab, y in (("analysis", x, ta, got[0]), ("synthesis", c, ts, got[1])):
+        want, A = want_legendre(which, src, tab), want_legendre(which, src, tab, absolute=True)
+        n = legendre_roundings(which, nlat, lmax)
+        yr = torch.view_as_real(y).numpy()
+        den = np.linalg.norm(want.ravel())
+        rel = float(np.linalg.norm((yr - want).ravel()) / den) if den > 0 else float(np.abs(yr).max())
+        ratio = worst_ratio(yr, want, A, n)
+        print(f"{name} {which} rel_l2 {rel:.1e} worst |err| / (gamma_N A) {ratio:.3f} (N={n})")
+        assert rel <= 1e-5 and ratio <= 1.0, (name, which, rel, ratio)
+        worst = max(worst, ratio)
+    ca, xs = got
+    for l in range(min(lmax, mmax - 1)):
+        assert torch.all(torch.view_as_real(ca[:, l, l + 1:].contiguous()) == 0)   # written in full, zeros for l < m
+    if mmax > lmax:
+        assert torch.all(torch.view_as_real(xs[:, :, lmax:].contiguous()) == 0)     # no l >= m below lmax
+    return worst
+
+
+def refused_legendre_arguments(lib, device="cpu"):
+    """every refused size returns its error before any launch"""
+    import pytest
+    from neuraloperator_amd import _lib
+    x = torch.zeros(2, 4, 3, dtype=torch.complex64, device=device)
+    tab = torch.zeros(4, 4, 3, device=device)
+    out = torch.full((2, 4, 3, 2), 7.0, device=device)
+    ptr = lambda t: t.data_ptr()
+    for bad in [(2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (-1, 4, 4, 3)]:
+        with pytest.raises(_lib.EngineError):
+            lib.legendre_analysis(ptr(x), ptr(tab), ptr(out), *bad)
+        with pytest.raises(_lib.EngineError):
+            lib.legendre_synthesis(ptr(x), ptr(tab), ptr(out), *bad)
+    lib.legendre_analysis(0, 0, 0, 0, 4, 4, 3)                  # no lines: nothing to do, no pointer read
+    assert torch.all(out.cpu() == 7.0)                          # no refused call launched anything

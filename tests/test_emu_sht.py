@@ -2,13 +2,16 @@
 emulation, against a float64 numpy einsum with the same tables: both grids, the three norms, Condon-Shortley phase on
 and off, odd nlat, mmax below / above lmax, lmax above nlat, more than one 64-column m group and one 16-row block (lmax = mmax = 72:
 the second group's synthesis starts at l = 64), line counts that are not a multiple of the per-lane tile; the adjoint
-identity of each kernel; size errors; a table off the operand's device is refused before any launch."""
+identity of each kernel; size errors; a table off the operand's device is refused before any launch.  The quick cases
+of the GPU tier (tests/test_gpu_sht_kernels.py: sht_reference.EMU_SHT_KERNEL_CASES) run here at the same two bars."""
 import numpy as np
 import pytest
 import torch
 
+import sht_reference as sr
 from emu_engine import engine_on_emulation
 from engine_runner import rel_l2
+from sht_reference import crandn as _crandn
 from neuraloperator_amd import _lib, engine
 from neuraloperator_amd.harmonics import _table
 
@@ -21,10 +24,6 @@ CASES = [("equiangular", "ortho", True, 9, 6, 4, 1),
          ("legendre-gauss", "ortho", True, 21, 18, 10, 9),
          ("equiangular", "ortho", False, 17, 20, 9, 4),
          ("equiangular", "ortho", True, 5, 72, 72, 2)]          # a second 64-column group with a non-empty sum
-
-
-def _crandn(g, *shape):
-    return torch.complex(torch.randn(*shape, generator=g), torch.randn(*shape, generator=g))
 
 
 @pytest.mark.parametrize("case", CASES, ids=[f"{c[0][:2]}-{c[1]}-cs{int(c[2])}-{c[3]}x{c[4]}x{c[5]}-L{c[6]}" for c in CASES])
@@ -82,13 +81,7 @@ def test_legendre_entry_points_reject_bad_sizes():
     with engine_on_emulation() as lib:
         x = torch.zeros(2, 4, 3, dtype=torch.complex64)
         tab = torch.zeros(4, 4, 3)
-        ptr = lambda t: t.data_ptr()
-        for bad in [(2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (-1, 4, 4, 3)]:
-            with pytest.raises(_lib.EngineError):
-                lib.legendre_analysis(ptr(x), ptr(tab), ptr(x), *bad)
-            with pytest.raises(_lib.EngineError):
-                lib.legendre_synthesis(ptr(x), ptr(tab), ptr(x), *bad)
-        lib.legendre_analysis(0, 0, 0, 0, 4, 4, 3)                  # no lines: nothing to do, no pointer read
+        sr.refused_legendre_arguments(lib)
         with pytest.raises(ValueError):
             engine.LegendreAnalysisFn.apply(x, tab[:, :3].contiguous())    # nlat of the table differs
         with pytest.raises(ValueError):
@@ -118,3 +111,12 @@ def test_legendre_refuses_a_table_off_the_operands_device(monkeypatch):
         engine.LegendreAnalysisFn.apply(x, tab.to("meta"))
     with pytest.raises(ValueError, match="device"):
         engine.LegendreSynthesisFn.apply(x, tab.to("meta"))
+
+
+@pytest.mark.parametrize("name", sr.EMU_SHT_KERNEL_CASES)
+def test_kernel_edge_cases_of_the_gpu_tier(name):
+    """the cases of tests/test_gpu_sht_kernels.py the emulation finishes quickly, at the same two bars"""
+    inputs = sr.sht_case_inputs(name, 91)
+    with engine_on_emulation() as lib:
+        got = sr.run_sht_case(lib, inputs)
+    sr.check_sht_case(name, inputs, got)

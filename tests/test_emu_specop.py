@@ -2,53 +2,19 @@
 numpy evaluation of its own formula with random complex tables: last kept extents 1, 4, 5, 33, 129 (and 300: waves side
 by side), row counts 1, 7, 64 (two non-last axes included), groups 1, 5, 33, one to three sources, an output without a
 term, both output layouts, conj, a spectrum at an address that is only 8-byte aligned; the adjoint identity; a
-bit-identical repeat; sizes, term counts and a table off the operand's device refused before any launch."""
+bit-identical repeat; sizes, term counts and a table off the operand's device refused before any launch.  The runner
+and the float64 formula are those of fourier_diff_reference, shared with the GPU tier
+(tests/test_gpu_specop_kernels.py), whose quick cases (EMU_SPECOP_KERNEL_CASES) run here at the same two bars."""
 import numpy as np
 import pytest
 import torch
 
+import fourier_diff_reference as fr
 from emu_engine import engine_on_emulation
 from engine_runner import rel_l2
+from fourier_diff_reference import crandn as _crandn, spec_tables as _tables, spec_terms as _terms, \
+    want_spectral_op as _want
 from neuraloperator_amd import _lib, engine
-
-
-def _crandn(g, *shape):
-    return torch.complex(torch.randn(*shape, generator=g), torch.randn(*shape, generator=g))
-
-
-def _tables(g, kept, n_tab):
-    a = [_crandn(g, n, k).contiguous() for n, k in zip(n_tab, kept)]
-    b = [_crandn(g, n, k).contiguous() for n, k in zip(n_tab, kept)]
-    return engine.SpectralTables(a, b)
-
-
-def _terms(g, n_src, n_out, n_tab, n_terms, empty=None):
-    """random terms; every output but `empty` gets at least one"""
-    ri = lambda hi: int(torch.randint(0, hi, (1,), generator=g))
-    outs = [o for o in range(n_out) if o != empty]
-    terms = []
-    for j in range(n_terms):
-        out = outs[j] if j < len(outs) else outs[ri(len(outs))]
-        terms.append((ri(n_src), out, float(torch.randn(1, generator=g)), tuple(ri(n) for n in n_tab)))
-    return tuple(terms)
-
-
-def _want(x, tabs, terms, n_out, conj):
-    """float64: y[g, t] = sum coef 1/2 (prod a + prod b) x[g, src]"""
-    x = x.numpy().astype(np.complex128)
-    kept = x.shape[2:]
-    y = np.zeros((x.shape[0], n_out) + kept, dtype=np.complex128)
-    for src, out, coef, tab in terms:
-        pa = np.ones(kept, dtype=np.complex128)
-        pb = np.ones(kept, dtype=np.complex128)
-        for d, r in enumerate(tab):
-            shp = [1] * len(kept)
-            shp[d] = kept[d]
-            pa = pa * tabs.a[d][r].numpy().astype(np.complex128).reshape(shp)
-            pb = pb * tabs.b[d][r].numpy().astype(np.complex128).reshape(shp)
-        gm = float(np.float32(coef)) * 0.5 * (pa + pb)
-        y[:, out] += (np.conj(gm) if conj else gm) * x[:, src]
-    return y
 
 
 # kept, groups, n_src, n_out, n_terms, empty output, conj, out_major
@@ -158,22 +124,9 @@ def test_bad_sizes_and_term_counts_are_refused():
     kept, n_tab = (4, 3), (2, 2)
     tabs = _tables(g, kept, n_tab)
     x = _crandn(g, 2, 2, *kept)
-    y = torch.zeros(2, 2, *kept, dtype=torch.complex64)
-    ok = dict(kept=kept, groups=2, n_src=2, n_out=2, terms=((0, 0, 1.0, (0, 0)), (1, 1, 1.0, (1, 1))),
-              tabs_a=[t.data_ptr() for t in tabs.a], tabs_b=[t.data_ptr() for t in tabs.b], n_tab=n_tab,
-              y_group_stride=24, y_out_stride=12)
+    ok = dict(terms=((0, 0, 1.0, (0, 0)), (1, 1, 1.0, (1, 1))))
     with engine_on_emulation() as lib:
-        xp, yp = torch.view_as_real(x).data_ptr(), torch.view_as_real(y).data_ptr()
-        lib.spectral_op(xp, yp, **ok)
-        bad = [dict(kept=(4, 0)), dict(kept=(4, 3, 2, 2)), dict(n_src=4), dict(n_src=0), dict(n_out=0), dict(n_out=13),
-               dict(groups=-1), dict(n_tab=(2, 0)), dict(terms=((2, 0, 1.0, (0, 0)),)), dict(terms=((0, 2, 1.0, (0, 0)),)),
-               dict(terms=((0, 0, 1.0, (0, 2)),)), dict(terms=((0, 0, 1.0, (0, 0)),) * 13), dict(y_out_stride=-1),
-               dict(n_out=12, terms=((0, 0, 1.0, (0, 0)),) * 2),            # 2 terms + 11 term-less outputs > 12 slots
-               dict(tabs_a=[0, 0])]
-        for change in bad:
-            with pytest.raises(_lib.EngineError):
-                lib.spectral_op(xp, yp, **{**ok, **change})
-        lib.spectral_op(0, 0, **{**ok, "groups": 0})                      # no groups: nothing to do, no pointer read
+        fr.refused_specop_arguments(lib)
         with pytest.raises(ValueError, match="tables for"):
             engine.SpectralOpFn.apply(x[..., :2], tabs, ok["terms"], 2)
         with pytest.raises(ValueError, match="outside"):
@@ -194,3 +147,13 @@ def test_tables_off_the_operands_device_are_refused(monkeypatch):
     monkeypatch.setattr(_lib, "_LIB", None)                                    # a launch would need the library
     with pytest.raises(ValueError, match="spectral tables on"):
         engine.SpectralOpFn.apply(x, meta, ((0, 0, 1.0, (0,)),), 1)
+
+
+@pytest.mark.parametrize("name", fr.EMU_SPECOP_KERNEL_CASES)
+def test_kernel_edge_cases_of_the_gpu_tier(name):
+    """the cases of tests/test_gpu_specop_kernels.py the emulation finishes quickly, at the same two bars"""
+    cfg = fr.SPECOP_KERNEL_CASES[name]
+    inputs = fr.specop_case_inputs(cfg, 91)
+    with engine_on_emulation() as lib:
+        got = fr.run_specop_case(lib, cfg, inputs)
+    fr.check_specop_case(name, cfg, inputs, got)

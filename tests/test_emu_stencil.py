@@ -3,7 +3,10 @@ emulation through the C-ABI against a float64 numpy evaluation of their own form
 lengths that are no multiple of the wave (1, 4, 5, 67, 130), many groups with tiny rows (33 x 4 x 5), more rows than one
 tile, periodic and clamped axes, the fused difference source, the per-group scale and the identity term; the adjoint
 identity of every finite-difference operator; the sums kernel with one and with several chunks per line and a point
-count that is no multiple of the chunk; bit-identical repeats; every refused argument returning its error."""
+count that is no multiple of the chunk; bit-identical repeats; every refused argument returning its error.  The runners
+and float64 formulas are those of finite_diff_reference, shared with the GPU tier (tests/test_gpu_stencil_kernels.py);
+the kernel-edge cases of that tier which the emulation finishes quickly (EMU_BAND_KERNEL_CASES, EMU_SUMS_KERNEL_CASES)
+run here at the same two bars, rel-L2 and per element |err| <= gamma_N A."""
 import numpy as np
 import pytest
 import torch
@@ -11,66 +14,9 @@ import torch
 import finite_diff_reference as fdr
 from emu_engine import engine_on_emulation
 from engine_runner import rel_l2
-from neuraloperator_amd import _lib, engine
-
-
-def _fold(idx, n, per):
-    return idx % n if per else np.clip(idx, 0, n - 1)
-
-
-def _random_tables(rng, dims, periodic, n_tab):
-    """[n_tab][n][7] per axis; on a clamped axis the taps that leave the line are zero, as the contract demands"""
-    tabs = []
-    for n, per, k in zip(dims, periodic, n_tab):
-        t = rng.standard_normal((k, n, 7))
-        if not per:
-            i = np.arange(n)[:, None] + np.arange(-3, 4)[None, :]
-            t[:, (i < 0) | (i >= n)] = 0
-        tabs.append(t.astype(np.float32))
-    return tabs
-
-
-def _want_band(u, u2, tabs, periodic, terms, n_out, scale):
-    s = u.astype(np.float64) - (0 if u2 is None else u2.astype(np.float64))
-    dims = s.shape[2:]
-    y = np.zeros((s.shape[0], n_out) + dims)
-    for src, out, coef, axis, tab in terms:
-        f = s[:, src]
-        if axis < 0:
-            y[:, out] += np.float32(coef) * f
-            continue
-        n = dims[axis]
-        shp = [1] * (1 + len(dims))
-        shp[1 + axis] = n
-        for o in range(-3, 4):
-            c = tabs[axis][tab][:, o + 3].astype(np.float64).reshape(shp)
-            y[:, out] += np.float32(coef) * c * np.take(f, _fold(np.arange(n) + o, n, periodic[axis]), axis=1 + axis)
-    return y * scale.reshape((-1,) + (1,) * (1 + len(dims)))
-
-
-def _terms(rng, n_src, n_out, ndim, n_tab, n_terms, empty=None):
-    outs = [o for o in range(n_out) if o != empty]
-    terms = []
-    for j in range(n_terms):
-        out = outs[j] if j < len(outs) else outs[rng.integers(len(outs))]
-        axis = int(rng.integers(-1, ndim)) if j else ndim - 1
-        terms.append((int(rng.integers(n_src)), out, float(rng.standard_normal()), axis,
-                      0 if axis < 0 else int(rng.integers(n_tab[axis]))))
-    return tuple(terms)
-
-
-def _band(lib, u, u2, tabs, periodic, terms, n_out, out_major, scale=None, scale_mul=None):
-    groups, n_src = u.shape[:2]
-    dims = tuple(u.shape[2:])
-    pts = int(np.prod(dims))
-    tt = [torch.from_numpy(t).contiguous() for t in tabs]
-    y = torch.full((n_out, groups, *dims) if out_major else (groups, n_out, *dims), float("nan"))
-    gs, os_ = (pts, groups * pts) if out_major else (n_out * pts, pts)
-    lib.band_apply(u.data_ptr(), 0 if u2 is None else u2.data_ptr(), y.data_ptr(), dims=dims, periodic=periodic,
-                   groups=groups, n_src=n_src, n_out=n_out, terms=terms, tabs=[t.data_ptr() for t in tt],
-                   n_tab=[t.shape[0] for t in tt], y_group_stride=gs, y_out_stride=os_,
-                   scale=0 if scale is None else scale.data_ptr(), scale_mul=0 if scale_mul is None else scale_mul.data_ptr())
-    return y.transpose(0, 1) if out_major else y
+from finite_diff_reference import random_tables as _random_tables, random_terms as _terms, run_band as _band, \
+    want_band as _want_band, want_sums as _want_sums
+from neuraloperator_amd import engine
 
 
 # dims, periodic, groups, n_src, n_out, n_terms, empty output, fused difference, scale, out_major
@@ -141,25 +87,6 @@ def test_adjoint_identity_of_every_operator(name):
                 assert abs(lhs - rhs) <= 1e-5 * (abs(lhs) + abs(rhs) + 1e-30), (axis, row)
 
 
-def _want_sums(x, y, d, h1, p, tabs, periodic):
-    x, y = x.astype(np.float64), y.astype(np.float64)
-    dims = x.shape[1:]
-    ax = tuple(range(1, 1 + d))
-
-    def terms(f):
-        out = [f]
-        for a in range(d if h1 else 0):
-            n = dims[a]
-            shp = [1] * (1 + d)
-            shp[1 + a] = n
-            out.append(sum(tabs[a][0][:, o + 3].astype(np.float64).reshape(shp) *
-                           np.take(f, _fold(np.arange(n) + o, n, periodic[a]), axis=1 + a) for o in range(-3, 4)))
-        return out
-    num = sum((np.abs(t) ** p).sum(axis=ax) for t in terms(x - y))
-    den = sum((np.abs(t) ** p).sum(axis=ax) for t in terms(y))
-    return num, den
-
-
 # dims, periodic, lines, h1, p, relative, root, mean, chunks asked for
 SUM_CASES = [((70, 130), (True, False), 1, True, 2, True, True, False, 0),      # several chunks (3 of 9 tiles each)
              ((70, 130), (True, False), 3, True, 2, False, True, True, 5),
@@ -228,55 +155,47 @@ def test_refused_arguments_return_their_error():
     rng = np.random.default_rng(1)
     dims, periodic = (4, 6), (False, True)
     tabs = [torch.from_numpy(t) for t in _random_tables(rng, dims, periodic, (2, 2))]
-    u, y = torch.zeros(2, 2, 4, 6), torch.zeros(2, 2, 4, 6)
-    ok = dict(dims=dims, periodic=periodic, groups=2, n_src=2, n_out=2, terms=((0, 0, 1.0, 0, 0), (1, 1, 1.0, -1, 0)),
-              tabs=[t.data_ptr() for t in tabs], n_tab=(2, 2), y_group_stride=48, y_out_stride=24)
+    u = torch.zeros(2, 2, 4, 6)
     with engine_on_emulation() as lib:
-        lib.band_apply(u.data_ptr(), 0, y.data_ptr(), **ok)
-        bad = [dict(dims=(4, 6, 2, 2)), dict(dims=(3, 6)), dict(dims=(4, 0)), dict(n_src=4), dict(n_src=0), dict(n_out=0),
-               dict(n_out=4), dict(groups=-1), dict(terms=((2, 0, 1.0, 0, 0),)), dict(terms=((0, 2, 1.0, 0, 0),)),
-               dict(terms=((0, 0, 1.0, 2, 0),)), dict(terms=((0, 0, 1.0, 0, 2),)), dict(terms=((0, 0, 1.0, 0, 0),) * 13),
-               dict(terms=((0, 0, 1.0, 0, 0),) * 12), dict(y_out_stride=-1), dict(tabs=[0, 0])]
-        for change in bad:
-            with pytest.raises(_lib.EngineError):
-                lib.band_apply(u.data_ptr(), 0, y.data_ptr(), **{**ok, **change})
-        with pytest.raises(_lib.EngineError):
-            lib.band_apply(0, 0, y.data_ptr(), **ok)
-        with pytest.raises(_lib.EngineError):
-            lib.band_apply(u.data_ptr(), 0, 0, **ok)
-        lib.band_apply(0, 0, 0, **{**ok, "groups": 0})                        # no groups: nothing to do
-        good = dict(dims=dims, periodic=periodic, lines=2, h1=True, relative=False, tabs=[t.data_ptr() for t in tabs])
-        x = torch.zeros(2, 4, 6)
-        v, dv, loss, ws = torch.zeros(2), torch.zeros(2), torch.full((1,), 5.0), torch.zeros(64)
-        args = lambda: (x.data_ptr(), x.data_ptr(), ws.data_ptr(), 256, v.data_ptr(), dv.data_ptr(), loss.data_ptr())
-        lib.sobolev_sums(lib.sobolev_desc(**good), *args())
-        assert float(loss) == 0.0
-        loss.fill_(5.0)
-        for change in [dict(dims=(3, 6)), dict(p=0, h1=False), dict(p=3), dict(lines=-1), dict(tabs=[0, 0]),
-                       dict(dims=(2, 6)), dict(chunks=-1)]:
-            desc = lib.sobolev_desc(**{**good, **change})
-            with pytest.raises(_lib.EngineError):
-                lib.sobolev_sums(desc, *args())
-            if "tabs" not in change:
-                assert lib.sobolev_workspace_bytes(desc) == 0
-        with pytest.raises(_lib.EngineError):
-            lib.sobolev_desc(**{**good, "dims": (4, 6, 2, 2)})
-        with pytest.raises(_lib.EngineError, match="workspace too small"):
-            lib.sobolev_sums(lib.sobolev_desc(**good), x.data_ptr(), x.data_ptr(), ws.data_ptr(), 8, v.data_ptr(),
-                             dv.data_ptr(), loss.data_ptr())
-        with pytest.raises(_lib.EngineError):
-            lib.sobolev_sums(lib.sobolev_desc(**good), 0, x.data_ptr(), ws.data_ptr(), 256, v.data_ptr(), dv.data_ptr(),
-                             loss.data_ptr())
-        with pytest.raises(_lib.EngineError):
-            lib.lp_grad(lib.sobolev_desc(**{**good, "h1": False, "p": 0}), *[x.data_ptr()] * 5)
-        with pytest.raises(_lib.EngineError):
-            lib.lp_grad(lib.sobolev_desc(**good), *[x.data_ptr()] * 5)            # H1 has no pointwise gradient
-        with pytest.raises(_lib.EngineError):
-            lib.lp_grad(lib.sobolev_desc(**{**good, "h1": False}), x.data_ptr(), 0, x.data_ptr(), x.data_ptr(), x.data_ptr())
-        assert float(loss) == 5.0                                              # no refused call launched anything
+        fdr.refused_stencil_arguments(lib)
         with pytest.raises(ValueError, match="tables for"):
             engine._band_apply(torch.zeros(1, 1, 4, 5), None, engine.BandTables(tabs, periodic, [(0, 1)] * 2), (), 1, False)
     with pytest.raises(AssertionError, match="outside its 7 bands"):
         engine.band_table(np.ones((9, 9)), False)
     with pytest.raises(RuntimeError, match="no CPU path"):
         engine._band_apply(u, None, engine.BandTables(tabs, periodic, [(0, 1)] * 2), (), 1, False)
+
+
+@pytest.mark.parametrize("name", fdr.EMU_BAND_KERNEL_CASES)
+def test_band_kernel_edge_cases_of_the_gpu_tier(name):
+    """the cases of tests/test_gpu_stencil_kernels.py the emulation finishes quickly, at the same two bars"""
+    cfg = fdr.BAND_KERNEL_CASES[name]
+    inputs = fdr.band_case_inputs(cfg, 91)
+    with engine_on_emulation() as lib:
+        got = fdr.run_band_case(lib, cfg, inputs)
+    fdr.check_band_case(name, cfg, inputs, got)
+
+
+@pytest.mark.parametrize("name", fdr.EMU_SUMS_KERNEL_CASES)
+def test_loss_kernel_edge_cases_of_the_gpu_tier(name):
+    cfg = fdr.SUMS_KERNEL_CASES[name]
+    inputs = fdr.sums_case_inputs(cfg, 93)
+    with engine_on_emulation() as lib:
+        got = fdr.run_sums_case(lib, cfg, inputs)
+        fdr.check_sums_case(name, cfg, inputs, got, lib)
+        assert got["n_chunks"] == fdr.sob_plan(cfg["dims"], cfg["h1"], cfg["lines"], cfg["chunks"])[1]
+
+
+@pytest.mark.parametrize("grid", [(1, 5, 6), (5, 2, 6), (5, 6, 3), (1, 1, 1)], ids=lambda g: "x".join(map(str, g)))
+def test_finite_diff_tables_of_the_smallest_periodic_extents(grid):
+    """the host's table builder owns the aliasing rule: D1 and D2 of every axis against the dense float64 matrices"""
+    h = (0.5, 1.25, 0.75)
+    u = torch.randn(2, 1, *grid, generator=torch.Generator().manual_seed(5))
+    with engine_on_emulation():
+        tabs = engine.finite_diff_tables(u.device, grid, h, (True,) * 3)
+        for axis in range(3):
+            for row in (0, 1):
+                got = engine._band_apply(u, None, tabs, ((0, 0, 1.0, axis, row),), 1, False)
+                want = fdr.apply_matrix(fdr.dense_matrix(grid[axis], h[axis], row + 1, True), u.double(), axis - 3)
+                scale = float(want.abs().max())
+                assert float((got.double() - want).abs().max()) <= 1e-5 * scale if scale else not got.any()
