@@ -2142,9 +2142,11 @@ extern "C" int sc_pointwise_block_forward(const sc_pmlp_desc* d, const float* co
 
 static int pmlp_bwd_waves(const sc_pmlp_desc*) { return 4; }
 static int pmlp_bwd_wgs(const sc_pmlp_desc* d) {
+  static const int env = [] { const char* e = SC_DIAG_ENV("SC_PMLP_BWD_WGS"); return e ? std::atoi(e) : 0; }();   // tests: the tile loop
   const int nw = pmlp_bwd_waves(d);
+  const int64_t cap = env > 0 && env < 256 ? env : 256;     // one workgroup per CU
   const int64_t wgs = (d->batch * (d->spatial / 32) + nw - 1) / nw;
-  return (int)(wgs < 256 ? wgs : 256);                      // one workgroup per CU
+  return (int)(wgs < cap ? wgs : cap);
 }
 
 template <int CI, int CH, int CO>

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import pointwise_reference as pr
 from engine_runner import emu_lib, rel_l2
 from neuraloperator_amd import _lib
 
@@ -24,11 +25,7 @@ def p(t):
 
 
 def _fwd_ref(x, w, b, skip, gate, flags):
-    xin = F.gelu(x) if flags & XACT else x
-    z = torch.einsum("oc,bcs->bos", w, xin) + (0 if b is None else b[None, :, None])
-    if skip is not None:
-        z = z + gate[None, :, None] * skip
-    return (F.gelu(z) if flags & ACT else z), z
+    return pr.plinx64(x, w, b, skip, gate, flags)            # float64: tests/pointwise_reference.py
 
 
 @pytest.mark.parametrize("ci,co", [(32, 64), (128, 64), (64, 128), (128, 128), (128, 32)])
@@ -171,3 +168,43 @@ def test_argument_checks(lib):
     with pytest.raises(_lib.EngineError):                # PRO without the pre-activation
         lib.pointwise_linear_backward_ex(1, 64, 128, 32, PRO, p(x), p(w), p(out), 0, 0, 0, 0, 0, p(x), p(w), 0, 0, 0, p(ws), 0)
     assert lib.pointwise_linear_workspace_bytes_ex(1, 48, 64, 32) == 0
+
+
+# ---- the kernel-edge tables of tests/pointwise_reference.py at the tile counts the emulated chip takes ---------------------
+EMU_A = [(kind, name) for kind in ("plinx_fwd", "plinx_bwd")
+         for name in pr.emu_subset(pr.TABLES[kind], lambda c: (c["ci"], c["co"], pr.instantiation("plinx_bwd", dict(c, want_gx=c.get("want_gx", 1)))))]
+
+
+@pytest.mark.parametrize("kind,name", EMU_A, ids=[f"{k}-{n}" for k, n in EMU_A])
+def test_tile_placement_inside_guard_bands(lib, kind, name):
+    """Table A at T <= 15 for every channel pair (and the LEAN instantiation): guard bands, per-element bounds, rel-L2.
+    One compute unit: k_plinx_fwd has 2 workgroups, k_plinx_bwd 1 or 2 -- T = 15 loops them"""
+    cfg = pr.TABLES[kind][name]
+    pr.run_case(kind, lib, cfg, guard=True, seed=11)
+
+
+LOOP_KINDS = [("plinx_fwd", dict(ci=ci, co=co, flags=XACT | ACT, gated=True, pre_out=1)) for ci, co in ((32, 32), (64, 128), (128, 128))]
+LOOP_KINDS += [("plinx_bwd", dict(ci=ci, co=co, flags=XACT | XGRAD | PRO, gated=True, addend=True, want_gx=1))
+               for ci, co in ((32, 32), (64, 128), (128, 128))]
+LOOP_KINDS += [("plinx_bwd", dict(ci=ci, co=co, flags=0, gated=False, addend=False, want_gx=0)) for ci, co in ((64, 64), (128, 128))]
+
+
+@pytest.mark.parametrize("kind,cfg", LOOP_KINDS, ids=[f"{k}-{c['ci']}_{c['co']}-gx{c.get('want_gx', '')}" for k, c in LOOP_KINDS])
+def test_nine_tiles_loop_on_one_compute_unit(lib, kind, cfg):
+    """the caps follow sc_cu_count() = 1 here (4 or 8 tiles per round): T = 9 is two or three rounds, the last ragged; for
+    the backward pass also with gout zero outside the last tile, tile 0 and the last tile of the first round"""
+    cap = pr.cap_of(kind, cfg, 1)
+    cfg = pr.with_tiles(cfg, 9)
+    assert 9 > 4 * cap
+    pr.run_case(kind, lib, cfg, seed=7, expect_n_wg=cap)
+    if kind == "plinx_bwd":
+        for tile in (8, 0, 4 * cap - 1):
+            got, _, _ = pr.run_case(kind, lib, cfg, seed=7, mark=tile, expect_n_wg=cap)
+            pr.assert_zero_outside_tile(got, cfg, tile)
+
+
+@pytest.mark.parametrize("tiles", [1, 9])
+def test_two_launches_share_one_partial_buffer_at_128_to_128(lib, tiles):
+    """om0 = 0 and 2: the second launch's final stage writes rows 64.. of gw / gb / ggate and leaves rows 0..63 alone"""
+    cfg = pr.with_tiles(dict(ci=128, co=128, flags=PRO, gated=True, addend=False, want_gx=1), tiles)
+    pr.run_case("plinx_bwd", lib, cfg, guard=True, seed=19, expect_n_wg=1)

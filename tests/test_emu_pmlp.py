@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import pointwise_reference as pr
 from engine_runner import emu_lib, rel_l2
 from neuraloperator_amd import _lib
 
@@ -18,11 +19,7 @@ def lib():
 
 
 def _ref(x, w1, b1, w2, b2, skip, gate, act):
-    h = F.gelu(torch.einsum("hc,bcs->bhs", w1.double(), x.double()) + (0 if b1 is None else b1.double()[None, :, None]))
-    z = torch.einsum("oh,bhs->bos", w2.double(), h) + (0 if b2 is None else b2.double()[None, :, None])
-    if skip is not None:
-        z = z + gate.double()[None, :, None] * skip.double()
-    return F.gelu(z) if act else z
+    return pr.mlp64(x, w1, b1, w2, b2, skip, gate, act)      # float64: tests/pointwise_reference.py
 
 
 @pytest.mark.parametrize("chans", [(32, 32, 32), (64, 32, 64), (64, 64, 64), (128, 64, 128)], ids=str)
@@ -121,6 +118,7 @@ def test_pointwise_linear(lib, c, bias):
     bd = None if b is None else b.double().requires_grad_(True)
     ref = torch.einsum("oc,bcs->bos", wd, xd) + (0 if bd is None else bd[None, :, None])
     assert rel_l2(out.numpy(), ref.detach().numpy()) < TOL
+    assert rel_l2(out.numpy(), pr.linear64(x, w, b).numpy()) < TOL
     if c == 128:
         assert lib.pointwise_linear_workspace_bytes(B, c, c, S) == 0        # forward only at 128 channels
         return
@@ -160,8 +158,7 @@ def test_pointwise_block_forward(lib, chans, act, bias):
     p = lambda t: 0 if t is None else t.data_ptr()
     lib.pointwise_block_forward(B, c, ch, S, act, p(conv), p(x), p(ws), p(bs), p(w1), p(b1), p(w2), p(b2), p(gt), p(y),
                                 p(pre) if act else 0, p(out), 0)
-    s_ref = conv.double() + torch.einsum("oc,bcs->bos", ws.double(), x.double()) + (0 if bs is None else bs.double()[None, :, None])
-    y_ref = F.gelu(s_ref) if act else s_ref
+    s_ref, y_ref, _ = pr.block64(conv, x, ws, bs, w1, b1, w2, b2, gt, act)
     out_ref = _ref(y_ref.float(), w1, b1, w2, b2, x, gt, act)
     assert rel_l2(y.numpy(), y_ref.numpy()) < TOL
     if act:
@@ -267,3 +264,43 @@ def test_block_backward_with_the_linear_skip_riding_along(lib, chans, act):
     assert rel_l2(gin1.numpy(), gin0.numpy()) < 1e-6
     assert rel_l2(glw1.numpy(), glw0.numpy()) < 1e-6 and rel_l2(glb1.numpy(), glb0.numpy()) < 1e-6
     assert not lib.pointwise_block_backward_supported(B, 64, 64, S)                    # tables + scratch + gradients > 160 KB
+
+
+# ---- the kernel-edge tables of tests/pointwise_reference.py at the tile counts the emulated chip takes ---------------------
+EMU_A = [(kind, name) for kind, key in (("mlp_fwd", "sid"), ("block_fwd", "sid"), ("mlp_bwd", "sid"), ("block_bwd", "sid"),
+                                        ("lin_fwd", "c"), ("lin_bwd", "c"))
+         for name in pr.emu_subset(pr.TABLES[kind], lambda c, k=key: c[k])]
+
+
+@pytest.mark.parametrize("kind,name", EMU_A, ids=[f"{k}-{n}" for k, n in EMU_A])
+def test_tile_placement_inside_guard_bands(lib, kind, name):
+    """Table A at T = 1, 3, 5, 15 (T = 5: two partials through both reduction stages), one variant per shape id: every
+    output, gradient and the workspace between guard bands, per-element bounds and the rel-L2 bar"""
+    cfg = pr.TABLES[kind][name]
+    pr.run_case(kind, lib, cfg, guard=True, seed=11, expect_n_wg=pr.n_wg_for(cfg["T"], pr.cap_of(kind, cfg, 1)))
+
+
+@pytest.mark.parametrize("c", [32, 64, 128])
+def test_linear_map_loops_its_tiles_on_one_compute_unit(lib, c):
+    """k_plin_fwd's grid is min(2, 160 KB / lds) workgroups per compute unit, one unit here: 9 tiles are two rounds"""
+    cap = pr.cap_of("lin_fwd", dict(c=c), 1)
+    assert cap == 2 and 9 > 4 * cap
+    pr.run_case("lin_fwd", lib, pr.with_tiles(dict(c=c, bias=1), 9), seed=5, expect_n_wg=cap)
+
+
+def test_the_activation_on_its_tails(lib):
+    """the scalar form with libm's exp2f and a division: the 1.5e-7 of the coded constants, on the host"""
+    got = pr.run_activation_routes(lib)
+    pr.check_activation(got)
+    names = list(got["gelu"])
+    for n in names[1:]:
+        assert torch.equal(got["gelu"][n].view(torch.int32), got["gelu"][names[0]].view(torch.int32)), n
+
+
+@pytest.mark.parametrize("kind,cfg", [("mlp_bwd", dict(chans=(64, 32, 64), gate=1, act=1, xpre=None, gbias=1, sid=212)),
+                                      ("lin_bwd", dict(c=64, addend=0, gbias=1))], ids=["mlp_bwd-212", "lin_bwd-64"])
+@pytest.mark.parametrize("n_wg", [17, 33])
+def test_reduction_stages_past_sixteen_partials(lib, kind, cfg, n_wg):
+    """k_pmlp_reduce1 sums partials y, y + 16, y + 32 in group y: 17 partials give group 0 two and the others one, 33 give
+    group 0 three -- below 17 every group holds one partial and the stride is never taken"""
+    pr.run_case(kind, lib, pr.with_tiles(cfg, 4 * n_wg - 3), guard=True, seed=19, expect_n_wg=n_wg)

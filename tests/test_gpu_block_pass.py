@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import pointwise_reference as pr
 from neuraloperator_amd import _lib
 from engine_runner import rel_l2
 
@@ -44,12 +45,7 @@ def test_block_pass_on_device(lib, c, ch, B, S, act):
     assert rel_l2(out.cpu().numpy(), out3.cpu().numpy()) < TOL
     # float64 (a slice of the large case)
     nb = min(B, 2)
-    xd, cd = x[:nb].double(), conv[:nb].double()
-    sd = cd + torch.einsum("oc,bcs->bos", ws.double(), xd) + bs.double()[None, :, None]
-    yd = F.gelu(sd) if act else sd
-    hd = F.gelu(torch.einsum("hc,bcs->bhs", w1.double(), yd) + b1.double()[None, :, None])
-    zd = torch.einsum("oh,bhs->bos", w2.double(), hd) + b2.double()[None, :, None] + gt.double()[None, :, None] * xd
-    od = F.gelu(zd) if act else zd
+    _, yd, od = pr.block64(conv[:nb], x[:nb], ws, bs, w1, b1, w2, b2, gt, act)
     assert rel_l2(y[:nb].cpu().numpy(), yd.cpu().numpy()) < TOL
     assert rel_l2(out[:nb].cpu().numpy(), od.cpu().numpy()) < TOL
 
@@ -83,9 +79,7 @@ def test_block_pass_derivative_form_on_device(lib):
     #  differences on the device, identical bits in host emulation, tests/test_emu_pmlp.py)
     close = lambda u, v: rel_l2(u.cpu().numpy(), v.cpu().numpy()) < 1e-6
     assert close(a[0], d[0]) and close(a[2], d[2])
-    t = a[1].double().requires_grad_(True)
-    F.gelu(t).backward(torch.ones_like(t))
-    assert rel_l2(d[1].cpu().numpy(), t.grad.cpu().numpy()) < TOL
+    assert rel_l2(d[1].cpu().numpy(), pr.dgelu64(a[1].double().cpu()).numpy()) < TOL
     for i in range(3, 10):
         assert close(a[i], d[i]), i
 
@@ -128,10 +122,5 @@ def test_block_backward_with_the_linear_skip_on_device(lib, act):
     for u, v in zip(d, a):
         assert close(u, v)
     # the gradient of the block input outside the spectral convolution, float64: d/dx of <out, gout> with conv held fixed
-    xd = x.double().requires_grad_(True)
-    sd = conv.double() + torch.einsum("oc,bcs->bos", ws.double(), xd) + bs.double()[None, :, None]
-    yd = F.gelu(sd) if act else sd
-    hd = F.gelu(torch.einsum("hc,bcs->bhs", w1.double(), yd) + b1.double()[None, :, None])
-    zd = torch.einsum("oh,bhs->bos", w2.double(), hd) + b2.double()[None, :, None] + gt.double()[None, :, None] * xd
-    (F.gelu(zd) if act else zd).backward(gout.double())
-    assert rel_l2(gin1.cpu().numpy(), xd.grad.cpu().numpy()) < TOL
+    _, (gin64,) = pr.grads64(lambda xd: pr.block64(conv, xd, ws, bs, w1, b1, w2, b2, gt, act)[2], [x], gout)
+    assert rel_l2(gin1.cpu().numpy(), gin64.numpy()) < TOL

@@ -1406,11 +1406,8 @@ def test_pointwise_mlp_pass(chans):
     mk = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc)
     x, sk, go = mk(3, ci, 24, 40), mk(3, co, 24, 40), mk(3, co, 24, 40)          # 960 pixels per sample
     w1, b1, w2, b2, gt = mk(ch, ci, 1, sc=ci ** -0.5), mk(ch), mk(co, ch, 1, sc=ch ** -0.5), mk(co), mk(1, co, 1, 1)
-    leaves = [t.double().requires_grad_(True) for t in (x, w1, b1, w2, b2, sk, gt)]
-    xd, w1d, b1d, w2d, b2d, skd, gtd = leaves
-    h = F.gelu(F.conv1d(xd.reshape(3, ci, -1), w1d, b1d))
-    ref = F.gelu(F.conv1d(h, w2d, b2d).reshape(3, co, 24, 40) + gtd * skd)
-    ref.backward(go.double())
+    import pointwise_reference as pr
+    ref, grads = pr.grads64(lambda *a: pr.mlp64(*a, act=1), (x, w1, b1, w2, b2, sk, gt), go)   # the float64 composition
     dl = [t.to(dev).requires_grad_(True) for t in (x, w1, b1, w2, b2, sk, gt)]
     with torch.no_grad():                                      # inference: every shape has the forward kernel
         out_ng = fused_channel_mlp(dl[0], dl[1], dl[2], dl[3], dl[4], skip_src=dl[5], gate=dl[6], activation="gelu")
@@ -1418,8 +1415,8 @@ def test_pointwise_mlp_pass(chans):
     out = fused_channel_mlp(dl[0], dl[1], dl[2], dl[3], dl[4], skip_src=dl[5], gate=dl[6], activation="gelu")
     out.backward(go.to(dev))
     assert rel_l2(out.detach().cpu().numpy(), ref.detach().numpy()) < TOL
-    for a, b in zip(dl, leaves):
-        assert rel_l2(a.grad.cpu().numpy(), b.grad.numpy()) < TOL
+    for a, b in zip(dl, grads):
+        assert rel_l2(a.grad.cpu().numpy(), b.numpy()) < TOL
 
 
 def _block_oracle(blk, x, g, index):
@@ -1537,11 +1534,8 @@ def test_two_pass_channel_mlp_and_rectangular_linear_maps(ci, ch, co):
     w1, b1 = torch.randn(ch, ci, 1, generator=g) / ci ** 0.5, torch.randn(ch, generator=g)
     w2, b2 = torch.randn(co, ch, 1, generator=g) / ch ** 0.5, torch.randn(co, generator=g)
     gate = torch.randn(1, co, 1, 1, generator=g)
-    leaves = [t.double().requires_grad_(True) for t in (x, w1, b1, w2, b2, skip, gate)]
-    xd, w1d, b1d, w2d, b2d, sd, gd = leaves
-    h = F.gelu(F.conv1d(xd.reshape(B, ci, -1), w1d, b1d))
-    ref = F.gelu(F.conv1d(h, w2d, b2d).reshape(B, co, H, W) + gd * sd)
-    ref.backward(go.double())
+    import pointwise_reference as pr
+    ref, grads = pr.grads64(lambda *a: pr.mlp64(*a, act=1), (x, w1, b1, w2, b2, skip, gate), go)
     dl = [t.to(dev).requires_grad_(True) for t in (x, w1, b1, w2, b2, skip, gate)]
     seen = []
     orig = nb.PointwiseMLP2Fn.apply
@@ -1553,12 +1547,12 @@ def test_two_pass_channel_mlp_and_rectangular_linear_maps(ci, ch, co):
     assert seen == [1]
     out.backward(go.to(dev))
     assert rel_l2(out.detach().cpu().numpy(), ref.detach().numpy()) < TOL
-    for a, b in zip(dl, leaves):
-        assert rel_l2(a.grad.cpu().numpy(), b.grad.numpy()) < TOL
+    for a, b in zip(dl, grads):
+        assert rel_l2(a.grad.cpu().numpy(), b.numpy()) < TOL
     # rectangular 1 x 1 map
     xl, wl, bl = (t.to(dev).requires_grad_(True) for t in (x, w1, b1))
     o2 = nb.fused_linear(xl, wl, bl)
-    r2 = F.conv1d(x.double().reshape(B, ci, -1), w1.double(), b1.double()).reshape(B, ch, H, W)
+    r2 = pr.linear64(x, w1, b1)
     assert o2.grad_fn is not None and "PointwiseLinear" in type(o2.grad_fn).__name__
     assert rel_l2(o2.detach().cpu().numpy(), r2.numpy()) < TOL
 
@@ -1571,15 +1565,14 @@ def test_pointwise_linear_pass(c):
     g = torch.Generator().manual_seed(c)
     x, go = torch.randn(3, c, 24, 40, generator=g), torch.randn(3, c, 24, 40, generator=g)
     w, b = torch.randn(c, c, 1, generator=g) / c ** 0.5, torch.randn(c, generator=g)
-    xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
-    ref = torch.nn.functional.conv1d(xd.reshape(3, c, -1), wd, bd).reshape(3, c, 24, 40)
-    ref.backward(go.double())
+    import pointwise_reference as pr
+    ref, grads = pr.grads64(pr.linear64, (x, w, b), go)
     xg, wg, bg = (t.to(dev).requires_grad_(True) for t in (x, w, b))
     out = fused_linear(xg, wg, bg)
     out.backward(go.to(dev))
-    assert rel_l2(out.detach().cpu().numpy(), ref.detach().numpy()) < TOL
-    for a, r in ((xg, xd), (wg, wd), (bg, bd)):
-        assert rel_l2(a.grad.cpu().numpy(), r.grad.numpy()) < TOL
+    assert rel_l2(out.detach().cpu().numpy(), ref.numpy()) < TOL
+    for a, r in zip((xg, wg, bg), grads):
+        assert rel_l2(a.grad.cpu().numpy(), r.numpy()) < TOL
 
 
 @pytest.mark.parametrize("grid", ["equiangular", "legendre-gauss"])
