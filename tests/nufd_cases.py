@@ -11,24 +11,56 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
+KNN_SENTINEL = 0x7FC0BEEF      # a NaN no kernel produces, compared as bits
+
+
+def knn_through_the_c_abi(cfg, data, queries):
+    """lib.knn on index and d2 buffers with m k sentinels (int64 -7, NaN) in front and behind: (index, d2) on the host,
+    the guards asserted intact"""
+    from neuraloperator_amd import _lib
+    lib, dev, mk = _lib.get_lib(), data.device, cfg["m"] * cfg["k"]
+    bi = torch.full((3 * mk,), -7, dtype=torch.int64, device=dev)
+    bd = torch.full((3 * mk,), KNN_SENTINEL, dtype=torch.int32, device=dev)
+    lib.knn(lib.knn_desc(cfg["d"], cfg["n"], cfg["m"], cfg["k"]), data.data_ptr(), queries.data_ptr(),
+            bi[mk:].data_ptr(), bd[mk:].data_ptr(), stream=engine._stream())
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    for buf, sent in ((bi, -7), (bd, KNN_SENTINEL)):
+        assert bool((buf[:mk] == sent).all()) and bool((buf[2 * mk:] == sent).all()), "a store outside index / d2"
+    shape = (cfg["m"], cfg["k"])
+    return _np(bi[mk:2 * mk].reshape(shape)), _np(bd[mk:2 * mk].view(torch.float32).reshape(shape))
+
+
 def run_knn(name, dev):
-    """sc_knn of m queries against n data points: sets and order against the float64 sort"""
+    """sc_knn of m queries against n data points: sets and order against the float64 sort on (d2 with NaN -> +inf,
+    index); +inf entries and rows without a near tie exactly; the same bits through the C-ABI on guarded buffers"""
     cfg = nr.KNN_CASES[name]
     data, queries = nr.knn_inputs(cfg)
     k = cfg["k"]
-    idx, d2 = engine.knn_search(torch.from_numpy(data).to(dev), torch.from_numpy(queries).to(dev), k)
+    td, tq = torch.from_numpy(data).to(dev), torch.from_numpy(queries).to(dev)
+    idx, d2 = engine.knn_search(td, tq, k)
     assert idx.dtype == torch.int64 and d2.dtype == torch.float32 and idx.shape == d2.shape == (cfg["m"], k)
     idx, d2 = _np(idx), _np(d2)
-    ridx, rd2 = nr.sorted_neighbours(data, queries, count=min(k + 1, cfg["n"]))
-    dist = np.sqrt(rd2)
-    tie = dist[:, k] - dist[:, k - 1] < nr.BAND * dist[:, k] if cfg["n"] > k else np.zeros(cfg["m"], bool)
-    print(f"{name}: {int(tie.sum())} of {cfg['m']} queries with a tie at the k-th neighbour")
+    ridx, rd2, tie, exact = nr.knn_expected(cfg, data, queries)
+    ridx, rd2 = ridx[:, :k], rd2[:, :k]
+    print(f"{name}: {int(tie.sum())} of {cfg['m']} queries with a tie at the k-th neighbour, {int(exact.sum())} rows exact")
     assert tie.mean() <= 0.05
-    assert idx.min() >= 0 and idx.max() < cfg["n"] and nr.order_ok(idx, d2)
-    assert nr.same_sets(idx[~tie], ridx[~tie, :k]).all()
-    np.testing.assert_allclose(d2[~tie], rd2[~tie, :k], rtol=1e-6, atol=0)    # both ascending
-    again = engine.knn_search(torch.from_numpy(data).to(dev), torch.from_numpy(queries).to(dev), k)
+    assert not np.isnan(d2).any() and idx.min() >= 0 and idx.max() < cfg["n"] and nr.order_ok(idx, d2)
+    assert nr.same_sets(idx[~tie], ridx[~tie]).all()
+    np.testing.assert_allclose(d2[~tie], rd2[~tie], rtol=1e-6, atol=0)        # both ascending
+    inf = np.isinf(rd2)                                      # NaN distances: +inf in ascending index, nothing to a band
+    assert np.array_equal(np.isinf(d2), inf) and np.array_equal(idx[inf], ridx[inf])
+    assert np.array_equal(idx[exact], ridx[exact])           # no near tie in the row: its order is determined
+    if cfg["kind"] == "few_finite":
+        assert inf[:, k - 4:].all() and not inf[:, :k - 4].any()
+    if cfg["kind"] == "nan_query":
+        assert np.array_equal(idx[4], np.arange(k)) and np.isinf(d2[4]).all() and not np.isinf(d2[[0, 8]]).any()
+    if cfg["kind"] == "nan_tenth":
+        assert not inf.any() and not np.isin(idx, np.arange(3, cfg["n"], 10)).any()
+    again = engine.knn_search(td, tq, k)
     assert np.array_equal(_np(again[0]), idx) and np.array_equal(_np(again[1]).view(np.int32), d2.view(np.int32))
+    cidx, cd2 = knn_through_the_c_abi(cfg, td, tq)
+    assert np.array_equal(cidx, idx) and np.array_equal(cd2.view(np.int32), d2.view(np.int32))
 
 
 def build_and_step(points, values, g, cfg, dev):

@@ -22,6 +22,7 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 U = 2.0 ** -24
 TILE, QPW, QPB, CAP = 1024, 8, 32, 128          # NUFD_TILE, NUFD_QPW, NUFD_QPB, NUFD_CAP of sc_kernels_nufd.h
+LANES = 64                                      # data points a wave takes at a time (the chunk loop of k_knn)
 LAMBDA = 1e-6
 BAND, MAX_COND, MAX_EXCLUDED = 1e-5, 1e3, 0.01
 
@@ -161,8 +162,9 @@ def same_sets(idx_got, idx_ref):
 
 def order_ok(idx, d2):
     """non-decreasing d2, ascending index among equal d2"""
-    dd, di = np.diff(np.asarray(d2), axis=1), np.diff(np.asarray(idx), axis=1)
-    return bool(np.all((dd > 0) | ((dd == 0) & (di > 0))))
+    d2, di = np.asarray(d2), np.diff(np.asarray(idx), axis=1)
+    a, b = d2[:, :-1], d2[:, 1:]                             # compared, not subtracted: +inf next to +inf is a tie
+    return bool(np.all((b > a) | ((b == a) & (di > 0))))
 
 
 # ---- recorded fixtures -------------------------------------------------------------------------------------------------
@@ -201,8 +203,11 @@ def case_inputs(cfg):
 
 
 # ---- free-standing descriptors (the emulation and the GPU tier run the same lists) ------------------------------------
-def knn_case(n, m, d, k, kind="rand"):
-    return dict(n=n, m=m, d=d, k=k, kind=kind)
+def knn_case(n, m, d, k, kind="rand", seed=None, emu=True):
+    """kind: rand; descending (every point improves the k best); nan_tenth (a tenth of the data points have a NaN
+    coordinate); few_finite (fewer than k finite data points); nan_query (one query has a NaN coordinate).  emu=False
+    keeps a case out of the emulation tier."""
+    return dict(n=n, m=m, d=d, k=k, kind=kind, seed=seed, emu=emu)
 
 
 # m = 37: a second workgroup with one wave of 5 queries and three empty waves; 70: a partly filled third workgroup
@@ -216,13 +221,66 @@ KNN_CASES = {
     "one_chunk_of_lanes": knn_case(64, 9, 3, 16),
     "every_point_improves": knn_case(3 * TILE - 40, 5, 1, 9, kind="descending"),
     "every_point_improves_k32": knn_case(2 * TILE + 3, 3, 1, 32, kind="descending"),
+    # the buffer of a query is ranked at the second and third chunk of 64 lanes, with k = 32 kept each time
+    "every_point_improves_n129_k32": knn_case(2 * LANES + 1, 3, 1, 32, kind="descending"),
+    # k = 32 is the largest the engine takes (NUFD_KMAX; sc_knn refuses 33): the whole cloud but one point
+    "all_but_one_point_n33_k32": knn_case(33, 33, 2, 32),
+    "nan_in_a_tenth_of_the_data": knn_case(300, 37, 3, 12, kind="nan_tenth"),
+    "fewer_than_k_finite_points": knn_case(200, 9, 2, 9, kind="few_finite"),
+    "a_query_with_a_nan": knn_case(100, 9, 2, 5, kind="nan_query"),
 }
+# query counts on the queries-per-wave (8) and per-workgroup (32) edges, the last workgroup partly filled
+for _m in (1, QPW - 1, QPW, QPW + 1, QPB - 1, QPB, QPB + 1, 2 * QPB + 1):
+    KNN_CASES[f"queries_m{_m}"] = knn_case(200, _m, 2, 5)
+# data counts on the 64-lane chunk: the first (cnt > 64) and the second compaction of a query's buffer
+for _n in (LANES - 1, LANES, LANES + 1, 2 * LANES - 1, 2 * LANES, 2 * LANES + 1):
+    for _k in (32, 3):
+        for _d in (1, 3):
+            KNN_CASES[f"lanes_n{_n}_k{_k}_d{_d}"] = knn_case(_n, 9, _d, _k)
+MAX_TIE_SHARE = 0.05
+
+
+def knn_expected(cfg, data, queries):
+    """(index (m, c), d2 (m, c), tie (m), exact (m)) of the float64 sort on (d2 with NaN -> +inf, index), c = min(k + 1,
+    n) columns.  tie: the k-th and (k + 1)-th distances are FINITE and within BAND (relative): which is the last
+    neighbour is not determined.  exact: every gap between consecutive finite distances of the c columns exceeds BAND, so
+    the fp32 rounding of d2 (a few 2^-24 relative) cannot reorder them: the whole index row is determined.  +inf entries
+    are ordered by index alone and are always determined."""
+    k, n = cfg["k"], cfg["n"]
+    p, q = np.asarray(data, np.float64), np.asarray(queries, np.float64)
+    d2 = ((q[:, None, :] - p[None, :, :]) ** 2).sum(-1)
+    d2[np.isnan(d2)] = np.inf
+    order = np.argsort(d2, axis=1, kind="stable")[:, :min(k + 1, n)]
+    d2 = np.take_along_axis(d2, order, axis=1)
+    dist = np.sqrt(d2)
+    with np.errstate(invalid="ignore"):
+        close = (dist[:, 1:] - dist[:, :-1] < BAND * dist[:, 1:]) & np.isfinite(dist[:, 1:])
+    tie = close[:, k - 1] if n > k else np.zeros(len(q), bool)
+    return order, d2, tie, ~close.any(1)
+
+
+def knn_tie_share(cfg):
+    data, queries = knn_inputs(cfg)
+    return float(knn_expected(cfg, data, queries)[2].mean())
 
 
 def knn_inputs(cfg):
     """(data (n, d), queries (m, d)) fp32"""
-    rng = np.random.default_rng(1000 * cfg["n"] + 10 * cfg["k"] + cfg["d"])
+    rng = np.random.default_rng(1000 * cfg["n"] + 10 * cfg["k"] + cfg["d"] if cfg.get("seed") is None else cfg["seed"])
     n, m, d = cfg["n"], cfg["m"], cfg["d"]
+    if cfg["kind"] in ("nan_tenth", "few_finite", "nan_query"):          # queries of their own: none is a NaN data point
+        data, queries = rng.random((n, d), dtype=np.float32), rng.random((m, d), dtype=np.float32)
+        if cfg["kind"] == "nan_tenth":
+            bad = np.arange(3, n, 10)
+            data[bad, bad % d] = np.nan
+        elif cfg["kind"] == "few_finite":                    # k - 4 finite points, most of them behind the first ranking
+            finite = np.array([3, 70, 130, 150, n - 1, 5, 90, 111])[:cfg["k"] - 4]
+            keep = data[finite].copy()
+            data[:, 0] = np.nan
+            data[finite] = keep
+        else:
+            queries[4, 1] = np.nan
+        return data, queries
     if cfg["kind"] == "descending":
         # 1-d points stored in descending distance from the last ones, which are the queries: every data point beats
         # the current k-th best, so the buffer fills and is ranked at every other chunk

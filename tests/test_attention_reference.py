@@ -197,3 +197,23 @@ def test_the_two_shape_failures_of_the_reference(emu):
     with pytest.raises(RuntimeError, match="size of tensor|must match"):  # 1-d rotary with batch > 1 dies in the repeat
         m(x, pos[..., :1], positional_embedding_module=emb)
     assert m.on_engine(x[:1], pos[:1, :, :1], positional_embedding_module=emb)
+
+
+def test_the_fp32_formula_alone_holds_the_row_bounds_on_the_whole_kernel_table():
+    """no engine: the plain formula with every tensor in fp32 (ar.manual_core; its layer-norm backward in float64, as the
+    kernels' own) against the float64 helper on every ar.ATTN_KERNEL_CASES entry -- rel-L2 <= 1e-5 per tensor and
+    ||err_row|| <= 1e-5 ||A_row|| per row (level 1 of DESIGN 3.26), so no case is too ill-conditioned for the bar; and the
+    same chain in float64 equals the autograd helper, so the two statements of the formula agree"""
+    worst = {}
+    for name, cfg in ar.ATTN_KERNEL_CASES.items():
+        args, ref = ar.kernel_reference(name)
+        common = args[:8] + (cfg["heads"], cfg["rotary"], args[8])
+        again = ar.manual_core(*common, torch.float64)
+        assert set(again) == set(ar.TENSORS)
+        for key, t in again.items():
+            assert ar.rel_l2(t.numpy(), ref[key][0].numpy()) <= 1e-12, (name, key)
+            assert bool((ref[key][1] >= ref[key][0].abs() * (1 - 1e-12)).all()), (name, key)     # A >= |value|
+        stats = ar.check_levels(name, cfg, ar.manual_core(*common, torch.float32), ref, element=False)
+        for key, (rel, row, _) in stats.items():
+            worst[key] = max(worst.get(key, (0.0, 0.0)), (row, rel))
+    print("worst (row ratio, rel-L2) of the fp32 formula:", {k: (round(a, 3), float(f"{b:.1e}")) for k, (a, b) in worst.items()})

@@ -1,7 +1,9 @@
 """CPU tier: the attention kernel integral kernels (sc_kernels_attn.h) in host emulation through the C-ABI against the
 float64 helper (tests/attention_reference.py): free-standing descriptors at the chunk and tile edges, every lane layout
 and rotary form, weights, n_qry != n_src, a point of zeros, the route, every refusal before any launch, bit-identical
-repeats, one gradient alone.  The emulation runs one OS thread per lane: tiny extents."""
+repeats, one gradient alone; and the part of the kernel table (ar.ATTN_KERNEL_CASES, emu=True) the thread-per-lane
+emulation can afford, on guarded buffers at the row and element bounds of DESIGN 3.26, with the workspace's
+intermediates.  The emulation runs one OS thread per lane: tiny extents."""
 import ctypes
 
 import pytest
@@ -29,6 +31,39 @@ def test_the_case_table_names_the_edges():
     assert any((c["heads"] * c["d"]) % 64 for c in CASES.values()) and any(c["batch"] == 3 for c in CASES.values())
     assert any(c["n_qry"] != c["n_src"] for c in CASES.values())
     assert any(ar.route_of(c["d"]) == ar.MFMA and c["n_src"] % ar.KSTEP for c in CASES.values())
+    # the kernel table (the device runs all of it, the emulation the cases with emu=True)
+    K = ar.ATTN_KERNEL_CASES.values()
+    on = lambda route, same=True: {c["n_src"] for c in K if ar.route_of(c["d"]) == route and                # noqa: E731
+                                   (c["n_src"] == c["n_qry"]) == same}
+    for d in (12, 32, 64, 128):                                          # T - 1, T, T + 1, 2 T, 2 T + 1 for T = 32, 128, 64
+        T = ar.tile_of(d)
+        assert T == {12: 32, 32: 128, 64: 128, 128: 64}[d]
+        assert {T - 1, T, T + 1, 2 * T, 2 * T + 1} <= {c["n_src"] for c in K if c["d"] == d}, d
+    for route in (ar.VECTOR, ar.MFMA):
+        assert {255, 256, 257, 256 + 31, 256 + 33, 511, 512, 513, 8 * 256 + 1} <= on(route), route
+        assert ar.chunks(8 * ar.CHUNK + 1) == 9
+        pairs = {(c["n_src"], c["n_qry"]) for c in K if ar.route_of(c["d"]) == route}
+        assert {(600, 40), (40, 600)} <= pairs and ar.chunks(600) == 3 and ar.chunks(40) == 1
+        assert {1, 2, 3} <= on(route)
+    assert {(600, 40), (40, 600)} <= {(c["n_src"], c["n_qry"]) for c in K if c["d"] == 128}
+    assert {2, 4, 28, 30, 34, 36, 60, 62, 66, 68, 100, 124, 126, 32, 64, 128} <= {c["d"] for c in K}
+    for d in ar.VECTOR_D + ar.MFMA_D:
+        assert {c["rotary"] for c in K if c["d"] == d} >= ({0, 1, 2} if d % 4 == 0 else {0, 1}), d
+    for d in (100, 124, 128):                                            # h > 0, a second batch and weights on DP = 128
+        assert any(c["d"] == d and c["heads"] == 3 and c["batch"] == 2 and c["weights"] for c in K), d
+    assert any((c["heads"] * c["d"]) % 32 for c in K) and any(c["weights"] == "signed" for c in K)
+    assert any(c["zero_point"] is not None and c["d"] == 64 for c in K) and any(c["const_row"] is not None for c in K)
+    for d in (12, 32, 128):
+        T = ar.tile_of(d)
+        assert {0, T - 1, T, 2 * T} <= {c["mark_g"] for c in K if c["d"] == d} and any(c["mark_q"] == T for c in K if c["d"] == d)
+    assert sorted(ar.dp_of(ar.ATTN_KERNEL_CASES[n]["d"]) for n in ar.WANT_CASES.values()) == [32, 32, 64, 64, 128, 128]
+    assert all(ar.ATTN_KERNEL_CASES[n]["n_src"] == ar.tile_of(ar.ATTN_KERNEL_CASES[n]["d"]) + 1 for n in ar.WANT_CASES.values())
+    assert len(ar.WANT_SUBSETS) == 7 and (True, True, True) in ar.WANT_SUBSETS
+    # the emulation's share: a case per DP of each route, both cross directions at D = 12, the marked points
+    E = [c for c in K if c["emu"]]
+    assert {(ar.route_of(c["d"]), ar.dp_of(c["d"])) for c in E} == {(r, p) for r in (ar.VECTOR, ar.MFMA) for p in (32, 64, 128)}
+    assert {(600, 40), (40, 600)} <= {(c["n_src"], c["n_qry"]) for c in E if c["d"] == 12}
+    assert sum(c["mark_g"] is not None for c in E) >= 8 and sum(c["mark_q"] is not None for c in E) >= 2
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -40,6 +75,44 @@ def test_against_the_float64_helper(emu, name):
     errs = ar.desc_errors(got, cfg, args)
     print(name, " ".join(f"{k} {e:.1e}" for k, e in errs.items()))
     assert max(errs.values()) <= ar.BAR, errs
+
+
+EMU_KERNEL_CASES = sorted(n for n, c in ar.ATTN_KERNEL_CASES.items() if c["emu"])
+
+
+@pytest.mark.parametrize("name", EMU_KERNEL_CASES)
+def test_kernel_table_on_guarded_buffers_at_the_row_and_element_bounds(emu, name):
+    got, stats = ar.run_kernel_case(emu, name)
+    assert set(stats) == set(ar.TENSORS)
+
+
+@pytest.mark.parametrize("kernel", sorted(ar.WANT_CASES))
+def test_every_subset_of_the_gradients_gives_the_bits_of_all_three(emu, kernel):
+    """the seven non-empty subsets of (gq, gk, gv) at n = T + 1: the wanted ones bit for bit those of the all-three run,
+    the others' guarded buffers and the workspace regions nobody needs untouched (asserted by the guarded run)"""
+    name = ar.WANT_CASES[kernel]
+    full, _ = ar.run_kernel_case(emu, name)
+    for want in ar.WANT_SUBSETS[:-1]:
+        part, _ = ar.run_kernel_case(emu, name, want=want)
+        for key, w in zip(("gq", "gk", "gv"), want):
+            assert (part[key] is not None) == w and (not w or torch.equal(part[key], full[key])), (want, key)
+        assert all(part[key] is None or torch.equal(part[key], full[key]) for key in ("u", "dots", "dots_t", "g_dots", "g_dots_t"))
+
+
+def test_a_point_of_zeros_adds_exactly_nothing_on_the_matrix_cores(emu):
+    """the zero-point property at D = 64: dots bit for bit the dots of the cloud without the point (one chunk each)"""
+    name = "zero_point_d64_one_chunk"
+    cfg = ar.ATTN_KERNEL_CASES[name]
+    (q, k, v, ps, pq, f, sc, w, g), _ = ar.kernel_reference(name)
+    z = cfg["zero_point"]
+    assert ar.route_of(cfg["d"]) == ar.MFMA and ar.chunks(cfg["n_src"]) == 1
+    assert float(k[:, z].abs().max()) == 0.0 == float(v[:, z].abs().max())
+    full = ar.run_descriptor(emu, cfg, q, k, v, ps, pq, f, sc, w, g, guard=True)
+    keep = [i for i in range(cfg["n_src"]) if i != z]
+    less = dict(cfg, n_src=cfg["n_src"] - 1, zero_point=None)
+    part = ar.run_descriptor(emu, less, q, k[:, keep], v[:, keep], ps[:, keep], pq, f, sc, w, g, want=(False, False, True),
+                             guard=True)
+    assert torch.equal(full[1], part[1]) and all(bool(torch.isfinite(t).all()) for t in full[:5])
 
 
 def test_a_point_of_zeros_adds_exactly_nothing(emu):

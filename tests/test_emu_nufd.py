@@ -21,7 +21,7 @@ def emu():
         yield lib
 
 
-@pytest.mark.parametrize("name", sorted(nr.KNN_CASES))
+@pytest.mark.parametrize("name", sorted(n for n, c in nr.KNN_CASES.items() if c["emu"]))
 def test_knn(emu, name):
     nc.run_knn(name, CPU)
 

@@ -53,7 +53,7 @@ def test_descriptors_against_the_float64_helper(name):
     from neuraloperator_amd import _lib
     cfg = ar.DESC_CASES[name]
     args = ar.desc_inputs(cfg, 41)
-    got = ar.run_descriptor(_lib.get_lib(), cfg, *args, device=DEV)
+    got = ar.run_descriptor(_lib.get_lib(), cfg, *args, device=DEV, guard=True)[:5]    # guards compared bit for bit
     assert all(bool(torch.isfinite(t).all()) for t in got)
     errs = ar.desc_errors(got, cfg, args)
     print(name, " ".join(f"{k}={e:.1e}" for k, e in errs.items()))

@@ -142,3 +142,18 @@ def test_ineligible_calls_stay_on_torch_and_the_engine_route_refuses_them():
     pg = p32.double().requires_grad_()
     D.non_uniform_fd(pg, v32.double(), num_neighbors=6).sum().backward()
     assert pg.grad is not None and bool(torch.isfinite(pg.grad).all())
+
+
+def test_tie_share_of_every_knn_case_from_the_float64_sort_alone():
+    """no engine: the share of queries whose k-th and (k + 1)-th finite distances lie within the band stays below the
+    cap on every KNN_CASES entry, so the seeds leave the comparisons their force; and the table names the edges"""
+    for name, cfg in nr.KNN_CASES.items():
+        assert nr.knn_tie_share(cfg) <= nr.MAX_TIE_SHARE == 0.05, name
+    K = nr.KNN_CASES.values()
+    assert {1, 7, 8, 9, 31, 32, 33, 65} <= {c["m"] for c in K if (c["n"], c["d"], c["k"]) == (200, 2, 5)}
+    for k in (32, 3):
+        for d in (1, 3):
+            assert {63, 64, 65, 127, 128, 129} <= {c["n"] for c in K if (c["k"], c["d"]) == (k, d)}, (k, d)
+    assert any(c["kind"] == "descending" and (c["n"], c["k"]) == (129, 32) for c in K)
+    assert any((c["n"], c["k"]) == (33, 32) for c in K) and {"nan_tenth", "few_finite", "nan_query"} <= {c["kind"] for c in K}
+    assert (nr.QPW, nr.QPB, nr.LANES) == (8, 32, 64)
