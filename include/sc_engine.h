@@ -90,7 +90,12 @@ enum {
                                 fp32 round-off class, 1.2e-7 from a float64 transform of the same values) instead of the
                                 default two (16 bits: 1.3e-6 -- 3000 x below the 2^-9 the bf16 input carries per value, 8 x
                                 below the 1e-5 bar of the fp32 gradients; 10 us per launch faster at the metric shape; round 6) */
-  SC_PLAN_IO_BF16 = 16       /* the REAL tensors (x, y, gy, gx) are bfloat16 in memory -- the `float*`
+  SC_PLAN_PLAIN_CACHE_POLICY = 1024, /* round 8 (A-B and tests): every spectrum leaves its kernel with plain stores and
+                                sc_layer_* asks the contractions for no cache policy -- round 7's policy at every site.
+                                Default: k_fft2d_fwd3 stores xhat / ghat write-through (nothing of them is dirty in the L2s
+                                at the kernel boundary); the contractions of sc_layer_* run round 7's policy either way
+                                (write-through yhat / gxhat and a streamed weight did not pay).  Same bits */
+  SC_PLAN_IO_BF16 = 16      /* the REAL tensors (x, y, gy, gx) are bfloat16 in memory -- the `float*`
                                 arguments that carry them then point at 2-byte elements; spectra,
                                 weights, bias and every arithmetic step stay float32 and y / gx are
                                 rounded to nearest even on the store (BASELINE configs[1] "bf16": the
@@ -143,6 +148,14 @@ enum {
                                 one-pass backward pair k_modegemm_sb_bwd mode tiles FASTEST (neighbouring workgroups stream
                                 neighbouring pieces of the same weight rows: 5.78 -> 5.54 ms per step at configs[4]) */
   SC_GEMM_NO_FMX = 1 << 24,  /* never take the matrix-core factor-matrix / mode-sum kernels (sc_kernels_fmx.h; A-B / tests) */
+  /* round 8, cache policy of the streamed matrix-core kernel (k_modegemm_dma / k_modegemm_dma_bwd; other routes ignore
+   * the three bits).  None of them changes a bit of C. */
+  SC_GEMM_C_WT = 1 << 26,    /* C IS consumed by the next kernel: write-through stores, no dirty lines at the kernel
+                                boundary (SC_GEMM_STREAM_C wins when both are set) */
+  SC_GEMM_NT_A = 1 << 27,    /* the caller calls A cold (not in the caches from an earlier kernel): its operand requests are
+                                non-temporal IF every piece of it has one reader in the launch (one column block, Q <= 32)
+                                and the launch runs the 4-wave shape; ignored otherwise */
+  SC_GEMM_NT_B = 1 << 28,    /* the same for B (one row block, P <= 32) */
   SC_GEMM_F16 = 32           /* the reference's complex-half contraction (fno_block_precision "half" / "mixed",
                               * einsum_utils.py:10-36): operands rounded to float16, four real products summed in
                               * fp32 and rounded to float16, re = t00 - t11, im = t10 + t01 rounded to float16;
@@ -190,6 +203,10 @@ int sc_modegemm_pair_fused(const sc_modegemm_desc* d0, const sc_modegemm_desc* d
  * profiles, like sc_modegemm_path): 2 = one launch of k_modegemm_sb_bwd, 1 = one launch of k_modegemm_dma_bwd,
  * 0 = two sc_modegemm launches. */
 int sc_modegemm_pair_path(const sc_modegemm_desc* d0, const sc_modegemm_desc* d1);
+/* The cache policy a sc_modegemm call with this descriptor runs with (introspection for tests, round 8): -1 when the call
+ * does not take the streamed matrix-core kernel (sc_modegemm_path != 2), else bits 0-1 = store policy of C (0 plain,
+ * 1 non-temporal, 2 write-through), bit 2 = A requested non-temporally, bit 3 = B requested non-temporally. */
+int sc_modegemm_policy(const sc_modegemm_desc* d);
 /* C[p, q] += sum_m sum_r opA(A[p, r, m]) * opB(B[r, q, m]) -- the gradient of a mode-independent
  * operand (Tucker / CP factor matrices, autograd of spectral_convolution.py:55-103): lanes run over
  * the modes, wave reduction, one atomic add per (p, q) and mode tile.  C (element offsets

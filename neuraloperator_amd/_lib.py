@@ -25,6 +25,7 @@ SC_PLAN_F2P_SMALL_ALWAYS = 64
 SC_PLAN_NO_SPAN = 128
 SC_PLAN_NO_MX_FFT = 256
 SC_PLAN_MX_FFT_3TERM = 512
+SC_PLAN_PLAIN_CACHE_POLICY = 1024
 SC_FREQ_DROPPED = -(1 << 63)
 SC_GEMM_FORCE_VALU = 1
 SC_GEMM_STREAM_C = 2
@@ -36,6 +37,9 @@ SC_GEMM_NO_SB = 64
 SC_GEMM_SB_WM4 = 128
 SC_GEMM_NO_FMX = 1 << 24
 SC_GEMM_SB_ALT_ORDER = 1 << 25
+SC_GEMM_C_WT = 1 << 26
+SC_GEMM_NT_A = 1 << 27
+SC_GEMM_NT_B = 1 << 28
 
 
 def SC_GEMM_GRID(n):
@@ -270,7 +274,7 @@ class ScEngineLib:
     # every symbol include/sc_engine.h declares
     SYMBOLS = ["sc_plan_create", "sc_plan_destroy", "sc_plan_workspace_bytes", "sc_plan_is_fast",
                "sc_transform_forward", "sc_transform_inverse", "sc_modegemm",
-               "sc_modegemm_msum", "sc_modegemm_msum_ws", "sc_modegemm_msum_workspace_bytes", "sc_modegemm_msum_path", "sc_modegemm_uses_matrix_cores", "sc_modegemm_path", "sc_bias_grad", "sc_adamw_step",
+               "sc_modegemm_msum", "sc_modegemm_msum_ws", "sc_modegemm_msum_workspace_bytes", "sc_modegemm_msum_path", "sc_modegemm_uses_matrix_cores", "sc_modegemm_path", "sc_modegemm_policy", "sc_bias_grad", "sc_adamw_step",
                "sc_layer_workspace_bytes", "sc_layer_forward", "sc_layer_backward",
                "sc_last_error", "sc_version", "sc_plan_kernel_name", "sc_transform_inverse_ex",
                "sc_layer_forward_ex", "sc_round_f16", "sc_pointwise_mlp_forward", "sc_pointwise_block_forward",
@@ -346,6 +350,8 @@ class ScEngineLib:
         L.sc_modegemm_uses_matrix_cores.restype = c_int
         L.sc_modegemm_path.argtypes = [POINTER(ModeGemmDesc)]
         L.sc_modegemm_path.restype = c_int
+        L.sc_modegemm_policy.argtypes = [POINTER(ModeGemmDesc)]
+        L.sc_modegemm_policy.restype = c_int
         L.sc_bias_grad.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]
         L.sc_bias_grad.restype = c_int
         L.sc_plan_workspace_bytes_sharded.argtypes = [c_void_p, c_int64]
@@ -1197,6 +1203,14 @@ class ScEngineLib:
         for k, v in kw.items():
             setattr(d, k, v)
         return int(self.lib.sc_modegemm_path(byref(d)))
+
+    def modegemm_policy(self, **kw):
+        """Cache policy of the streamed route: -1 = another route; else bits 0-1 the store policy of C (0 plain, 1
+        non-temporal, 2 write-through), bit 2 = A requested non-temporally, bit 3 = B (SC_GEMM_C_WT / _NT_A / _NT_B)."""
+        d = ModeGemmDesc()
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return int(self.lib.sc_modegemm_policy(byref(d)))
 
     def adamw_step(self, p_ptr, g_ptr, m_ptr, v_ptr, n, is_complex, stream=0, *, lr, beta1, beta2, eps,
                    weight_decay, correct_bias, step):

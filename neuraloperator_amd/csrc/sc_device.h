@@ -73,9 +73,15 @@ SC_DEVICE int sc_opaque_s(int x) {
 // piece at the wave-uniform LDS address `lbase` (lane l lands at lbase + 16 l); the global source is per lane.
 // hipcc neither counts these operations nor orders ds_reads behind them: the kernel waits with its own counted
 // s_waitcnt vmcnt(N) and a raw s_barrier (cdna_hip_programming.md 5, "Pipelining across barriers").
-#define SC_GLDS16(gptr, lbase)                                                                   \
+// `aux` is the request's cache policy, a compile-time constant: SC_AUX_DEFAULT, or SC_AUX_NT for bytes that exactly ONE
+// workgroup of the launch reads and that are cold when it starts (a weight read once per launch): streamed, they do not
+// push the operands other workgroups share out of the caches.  nt on bytes several units re-read costs time.
+#define SC_AUX_DEFAULT 0
+#define SC_AUX_NT 2
+#define SC_GLDS16_AUX(gptr, lbase, aux)                                                          \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),        \
-                                   (__attribute__((address_space(3))) void*)(lbase), 16, 0, 0)
+                                   (__attribute__((address_space(3))) void*)(lbase), 16, 0, (aux))
+#define SC_GLDS16(gptr, lbase) SC_GLDS16_AUX(gptr, lbase, SC_AUX_DEFAULT)
 template <int N>
 SC_DEVICE void sc_wait_vmcnt() {        // at most N of this wave's vector-memory operations still in flight
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -253,7 +259,10 @@ struct alignas(16) sc_f4 {
 // LDS-DMA emulated as a synchronous copy by the lane's own thread; the waits are no-ops, the raw barrier is the
 // workgroup barrier -- ordering bugs that depend on a MISSING wait are therefore invisible here (the GPU tier
 // and the counted-wait arithmetic in the kernel comments cover those), index maths and buffer rotation are not
-#define SC_GLDS16(gptr, lbase) std::memcpy(reinterpret_cast<unsigned char*>(lbase) + 16 * (SC_TID & 63), (gptr), 16)
+#define SC_AUX_DEFAULT 0
+#define SC_AUX_NT 2
+#define SC_GLDS16_AUX(gptr, lbase, aux) std::memcpy(reinterpret_cast<unsigned char*>(lbase) + 16 * (SC_TID & 63), (gptr), 16)
+#define SC_GLDS16(gptr, lbase) SC_GLDS16_AUX(gptr, lbase, SC_AUX_DEFAULT)
 template <int N>
 inline void sc_wait_vmcnt() {}
 #define SC_WAIT_LGKM0() do { } while (0)
@@ -438,6 +447,66 @@ inline cf32 sc_gload8_untracked(const cf32* p) { return *p; }
 inline float sc_gload4_untracked(const float* p) { return *p; }
 inline void sc_landed(cf32&) {}
 inline void sc_landed(float&) {}
+#endif
+// ---- store policy of a spectrum that the NEXT kernel reads (xhat, yhat, ghat, gxhat: 34.6 MB at the metric shape).
+// The eight L2s are write-back and private to their XCDs: a plain store leaves its line dirty in the writer's L2, and the
+// write-back of what is still dirty when the kernel ends is paid at the kernel boundary, before the consumer (which runs
+// on other XCDs) may read.  SC_ST_WT stores write through (sc1): the bytes leave L2 while the producer still computes and
+// nothing is dirty at its end.  SC_ST_NT is the streaming policy of the real tensors.  No policy changes a stored bit.
+#define SC_ST_PLAIN 0
+#define SC_ST_NT 1
+#define SC_ST_WT 2
+#ifndef SC_EMU
+typedef unsigned int sc_u4 __attribute__((ext_vector_type(4)));
+// 16 bytes at a per-lane 64-bit address (no 32-bit offset anywhere: arrays beyond 2^31 bytes are fine).  The store is
+// inline assembly because a write-through store of 16 bytes has no builtin with a global address; the s_nop keeps the
+// compiler's next instruction off the data registers until the store has read them.  vmcnt counts it like any store.
+SC_DEVICE void sc_store16_wt(void* dst, const sc_f4 v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+}
+SC_DEVICE void sc_store8_wt(cf32* dst, const cf32 v) {
+  typedef __attribute__((address_space(1))) unsigned long long gu64_;
+  const unsigned long long bits = ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x);
+  __hip_atomic_store((gu64_*)dst, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // global_store_dwordx2 ... sc1
+}
+SC_DEVICE void sc_store8_nt(cf32* dst, const cf32 v) {
+  typedef float f2v_ __attribute__((ext_vector_type(2)));
+  f2v_ t;
+  t.x = v.x;
+  t.y = v.y;
+  __builtin_nontemporal_store(t, reinterpret_cast<f2v_*>(dst));
+}
+// 16-byte pieces of ONE contiguous block (an image's kept block): the block's base and size sit in a buffer resource
+// (wave-uniform), the lane passes a 32-bit byte offset inside the block; pieces past `bytes` are dropped by the hardware
+struct sc_block16 {
+  __amdgpu_buffer_rsrc_t rs;
+  sc_f4* base;
+};
+SC_DEVICE sc_block16 sc_block16_make(void* base, const int bytes) {
+  sc_block16 b;
+  b.rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+  b.base = reinterpret_cast<sc_f4*>(base);
+  return b;
+}
+template <int POLICY>
+SC_DEVICE void sc_block16_store(const sc_block16& b, const int piece, const sc_f4 v) {
+  if (POLICY == SC_ST_WT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sc_u4, v), b.rs, piece * 16, 0, 16);
+  else if (POLICY == SC_ST_NT) __builtin_nontemporal_store(v, b.base + piece);
+  else b.base[piece] = v;
+}
+#else
+inline void sc_store16_wt(void* dst, const sc_f4 v) { std::memcpy(dst, &v, 16); }
+inline void sc_store8_wt(cf32* dst, const cf32 v) { std::memcpy(dst, &v, 8); }
+inline void sc_store8_nt(cf32* dst, const cf32 v) { std::memcpy(dst, &v, 8); }
+struct sc_block16 {
+  unsigned char* base;
+  int bytes;
+};
+inline sc_block16 sc_block16_make(void* base, const int bytes) { return sc_block16{reinterpret_cast<unsigned char*>(base), bytes}; }
+template <int POLICY>
+inline void sc_block16_store(const sc_block16& b, const int piece, const sc_f4 v) {
+  if (piece * 16 + 16 <= b.bytes) std::memcpy(b.base + piece * 16, &v, 16);
+}
 #endif
 // acc += a * b
 SC_HD void cf_mac(cf32& acc, const cf32 a, const cf32 b) {

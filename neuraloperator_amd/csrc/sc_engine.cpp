@@ -1511,6 +1511,39 @@ static int run_axis(int jt, const cf32* in, cf32* out, const DeviceTable& t, int
 // ------------------------------------------------------------------------------------------
 // transforms
 // ------------------------------------------------------------------------------------------
+// Round 8: the cache policy of the spectra and of the weight, site by site.  A set bit = the site runs
+// its round-8 policy; SC_PLAN_PLAIN_CACHE_POLICY clears them all (round 7's policy everywhere).  Measurement builds
+// (-DSC_DIAG) read SC_POLICY_SITES = <mask> from the environment in place of the default, and SC_POLICY_NT = <mask of
+// store sites> whose stores are non-temporal instead of write-through (scripts/boundary_table.py).
+enum {
+  SC_SITE_XHAT_ST = 1,     // k_fft2d_fwd3, SC_FWD_SCALED: xhat
+  SC_SITE_GHAT_ST = 2,     // k_fft2d_fwd3, SC_FWD_ADJ_C2R: ghat
+  SC_SITE_YHAT_ST = 4,     // sc_layer_forward: yhat of the contraction
+  SC_SITE_GXHAT_ST = 8,    // sc_layer_backward: gxhat of the gradient-of-the-spectrum job
+  SC_SITE_W_NT_FWD = 16,   // sc_layer_forward: the weight requested non-temporally
+  SC_SITE_W_NT_BWD = 32    // sc_layer_backward: the same in the gradient-of-the-spectrum job
+};
+// Default: the two write-through stores of k_fft2d_fwd3 (producer + consumer -4.4 / -5.0 us each against a spread of
+// ~2 us, profiles/r08_boundaries.txt).  Write-through yhat / gxhat measured -1.6 / -1.7 us, inside the 3-6 us spread
+// of their producer + consumer spans: not a gain by the round's rule, so the contractions of sc_layer_* keep plain stores.
+// The two non-temporal weight sites LOST and stay off: the weight (69 MB at the metric shape) survives in the Infinity
+// Cache from one use to the next, and a streamed read gives that up -- forward product 36 -> 52 us, pair 60 -> 74 us and
+// the forward product of the NEXT step 36 -> 41 us.
+#ifndef SC_POLICY_DEFAULT_SITES
+#define SC_POLICY_DEFAULT_SITES (SC_SITE_XHAT_ST | SC_SITE_GHAT_ST)
+#endif
+static int policy_sites(const sc_plan* p) {
+  if (p->d.flags & SC_PLAN_PLAIN_CACHE_POLICY) return 0;
+  static const int sites = [] { const char* e = SC_DIAG_ENV("SC_POLICY_SITES"); return e ? std::atoi(e) : (int)SC_POLICY_DEFAULT_SITES; }();
+  return sites;
+}
+// store policy (sc_device.h SC_ST_*) of a spectrum-store site
+static int policy_store(const sc_plan* p, const int site) {
+  if (!(policy_sites(p) & site)) return SC_ST_PLAIN;
+  static const int nt = [] { const char* e = SC_DIAG_ENV("SC_POLICY_NT"); return e ? std::atoi(e) : 0; }();
+  return (nt & site) ? SC_ST_NT : SC_ST_WT;
+}
+
 static int transform_forward_impl(const sc_plan* p, int mode, const float* x, float* xhat, int64_t n_images,
                                   void* workspace, void* stream, F3Shard sh);
 
@@ -1533,9 +1566,11 @@ static int transform_forward_impl(const sc_plan* p, int mode, const float* x, fl
     if (p->d.flags & SC_PLAN_IO_BF16) {
       if (p->fft2d.tabF && !((uintptr_t)x & 15))           // round 5: the row pass on the matrix cores (16-byte row loads)
         return fft3mx_forward(&p->fft2d, mode, (const sc_bf16*)x, (cf32*)xhat, n_images, st, &g_last_error, sh);
-      return fft3_forward(&p->fft2d, mode, (const sc_bf16*)x, (cf32*)xhat, n_images, st, &g_last_error, sh);
+      return fft3_forward(&p->fft2d, mode, (const sc_bf16*)x, (cf32*)xhat, n_images, st, &g_last_error, sh,
+                          policy_store(p, mode == SC_FWD_SCALED ? SC_SITE_XHAT_ST : SC_SITE_GHAT_ST));
     }
-    return fft3_forward(&p->fft2d, mode, x, (cf32*)xhat, n_images, st, &g_last_error, sh);
+    return fft3_forward(&p->fft2d, mode, x, (cf32*)xhat, n_images, st, &g_last_error, sh,
+                        policy_store(p, mode == SC_FWD_SCALED ? SC_SITE_XHAT_ST : SC_SITE_GHAT_ST));
   }
   if (p->f2p) return f2p_forward(p, mode, x, (cf32*)xhat, n_images, workspace, st);
   const int L = p->nd - 1;
@@ -3240,6 +3275,16 @@ extern "C" int sc_layer_forward_ex(const sc_plan* p, const sc_layer_desc* L, con
   g.b_sr = Co * Wm; g.b_sq = Wm; g.b_sm = 1; g.b_idx = idx;
   g.c_sp = Co * Mk; g.c_sq = Mk; g.c_sm = 1;
   g.flags = (p->d.flags & SC_PLAN_FORCE_GENERIC) ? SC_GEMM_FORCE_VALU : 0;
+  // cache policy sites of round 8 (honoured by the streamed kernel only; both OFF by default, policy_sites): yhat is read
+  // by the inverse transform next -> write-through stores; with one row block (B <= 32) each piece of the weight has one
+  // reader -> non-temporal requests.  xhat is shared by the column blocks: always default requests.  In the product
+  // library neither branch below is ever taken (the sites are reachable only through SC_POLICY_SITES of a -DSC_DIAG
+  // build); the one test that runs them is the emulation tier's (tests/test_emu_cache_policy.py, a child process).
+  if (!g.flags) {
+    const int ps = policy_store(p, SC_SITE_YHAT_ST);
+    g.flags |= ps == SC_ST_WT ? SC_GEMM_C_WT : (ps == SC_ST_NT ? SC_GEMM_STREAM_C : 0);
+    if (policy_sites(p) & SC_SITE_W_NT_FWD) g.flags |= SC_GEMM_NT_B;
+  }
   rc = sc_modegemm(&g, xhat_saved, w, yhat, stream);
   if (rc) return rc;
   return sc_transform_inverse_ex(p, SC_INV_PADDED, yhat, bias, Co, ep, y, B * Co, ws, stream);
@@ -3294,6 +3339,14 @@ extern "C" int sc_layer_backward_ex(const sc_plan* p, const sc_layer_desc* L, co
   dx.b_sr = Wm; dx.b_sq = Co * Wm; dx.b_sm = 1; dx.b_idx = idx; dx.conj_b = 1;
   dx.c_sp = Ci * Mk; dx.c_sq = Mk; dx.c_sm = 1;
   dx.flags = gflags;
+  // cache policy sites of round 8 (as in sc_layer_forward_ex, both OFF by default): gxhat is read by the inverse transform
+  // next -> write-through; the weight, with one row block, is read once -> non-temporal.  ghat is read by both jobs:
+  // default.  gW: non-temporal as before.  Never taken in the product library, as there
+  if (!gflags) {
+    const int ps = policy_store(p, SC_SITE_GXHAT_ST);
+    dx.flags |= ps == SC_ST_WT ? SC_GEMM_C_WT : (ps == SC_ST_NT ? SC_GEMM_STREAM_C : 0);
+    if (policy_sites(p) & SC_SITE_W_NT_BWD) dx.flags |= SC_GEMM_NT_B;
+  }
   bool paired = false;
   if (gw && gx && !idx) {
     // small batch against a large weight (BASELINE configs[4]): ONE pass over W for both gradients

@@ -434,7 +434,15 @@ static bool gemm8_args(const sc_modegemm_desc* d, Gemm8Args& g, int64_t resident
   g.a_sg = d->a_sg ? d->a_sg : 16;                            // groups of 16 modes (plain arrays: 16 apart)
   g.b_sg = d->b_sg ? d->b_sg : 16;
   g.c_sg = d->c_sg ? d->c_sg : 16;
-  g.stream_c = (d->flags & SC_GEMM_STREAM_C) ? 1 : 0;
+  // cache policy (round 8).  C: non-temporal when nobody reads it next, write-through when the next kernel does.
+  // Operands: a piece of A is read by the n_qb tiles of its (row block, mode group), a piece of B by the n_pb tiles of
+  // its (column block, mode group) -- with ONE block on that side every piece has exactly one reader in the launch, and
+  // if the caller also says the operand is cold (SC_GEMM_NT_A / _B) its requests are non-temporal.  An operand several
+  // workgroups share, or one that an earlier kernel left in the caches, keeps the default: nt on re-read bytes costs time.
+  // The 8-wave shape issues its requests between MFMAs and keeps the one request form it was tuned with.
+  g.stream_c = (d->flags & SC_GEMM_STREAM_C) ? SC_ST_NT : ((d->flags & SC_GEMM_C_WT) ? SC_ST_WT : SC_ST_PLAIN);
+  g.nt_a = (!wide && (d->flags & SC_GEMM_NT_A) && g.n_qb == 1) ? 1 : 0;
+  g.nt_b = (!wide && (d->flags & SC_GEMM_NT_B) && g.n_pb == 1) ? 1 : 0;
   // tiles per workgroup: a launch a little larger than what the chip holds at once runs its tiles back to back
   // inside fewer workgroups instead of queueing a short second round
   const int64_t nblk = (int64_t)g.n_pb * g.n_qb;
@@ -569,6 +577,13 @@ extern "C" int sc_modegemm_path(const sc_modegemm_desc* d) {
   if (sb_gemm_eligible(d, nullptr, nullptr, nullptr)) return 3;
   if (gemm8_eligible(d, nullptr, nullptr, nullptr)) return 2;
   return !(d->flags & SC_GEMM_FORCE_VALU) && mfma_gemm_eligible(d) ? 1 : 0;
+}
+
+extern "C" int sc_modegemm_policy(const sc_modegemm_desc* d) {
+  if (!d || sc_modegemm_path(d) != 2) return -1;
+  Gemm8Args g;
+  gemm8_args(d, g, SC_G8_RESIDENT(false), SC_G8_RESIDENT(true), -1);
+  return g.stream_c | (g.nt_a << 2) | (g.nt_b << 3);
 }
 
 extern "C" int sc_modegemm_uses_matrix_cores(const sc_modegemm_desc* d) {

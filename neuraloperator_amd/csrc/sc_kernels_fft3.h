@@ -119,6 +119,8 @@ SC_DEVICE void f3_store_epi(IO* row, const float sk, IO* prow, const int lam, co
 struct F3Shard {
   int rows;
   int64_t block_stride;      // complex elements between blocks
+  int st_pol;                // k_fft2d_fwd3 only: store policy of the spectrum (sc_device.h SC_ST_*; rides here, last, so that
+                             // F3Shard{rows, stride} means SC_ST_PLAIN and the kernel's signature stays what it was)
 };
 SC_HD int64_t f3_shard_index(const F3Shard sh, const int64_t img, const int i, const int My) {
   const int row = i / My, col = i - row * My;
@@ -487,11 +489,38 @@ k_fft2d_fwd3(const IO* __restrict__ x, cf32* __restrict__ xhat, const cf32* __re
     }
   }
   SC_SYNC();
+  // Round 8: the next kernel reads this block on other XCDs, so with SC_ST_WT / SC_ST_NT nothing of it stays dirty in this
+  // XCD's L2 for the kernel boundary to write back (sc_device.h).  Plain layout: the image's block is contiguous -- 16-byte
+  // pieces through a buffer resource that holds the block's base (64-bit) and size whenever the block starts on a 16-byte
+  // boundary and has an even number of coefficients (the metric shape: 16 896 bytes); else, and in the sharded layout
+  // (rows of My coefficients at scattered places), 8-byte pieces.  SC_ST_PLAIN is the loop of rounds 1-7.
+  const int pol = SC_UNIFORM(sh.st_pol);
   if (sh.rows <= 0) {
     cf32* dst = xhat + img * (int64_t)Mx * My;
-    for (int i = tid; i < Mx * My; i += 256) dst[i] = OUT[i];
+    const int n = Mx * My;
+    if (pol == SC_ST_PLAIN) {
+      for (int i = tid; i < n; i += 256) dst[i] = OUT[i];
+    } else if (((n & 1) == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+      const sc_f4* OUT4 = reinterpret_cast<const sc_f4*>(OUT);
+      const sc_block16 blk = sc_block16_make(dst, n * 8);
+      if (pol == SC_ST_WT) {
+        for (int i = tid; i < (n >> 1); i += 256) sc_block16_store<SC_ST_WT>(blk, i, OUT4[i]);
+      } else {
+        for (int i = tid; i < (n >> 1); i += 256) sc_block16_store<SC_ST_NT>(blk, i, OUT4[i]);
+      }
+    } else if (pol == SC_ST_WT) {
+      for (int i = tid; i < n; i += 256) sc_store8_wt(dst + i, OUT[i]);
+    } else {
+      for (int i = tid; i < n; i += 256) sc_store8_nt(dst + i, OUT[i]);
+    }
   } else {                                                // sharded spectrum (include/sc_engine.h, sc_spectrum_shards)
-    for (int i = tid; i < Mx * My; i += 256) xhat[f3_shard_index(sh, img, i, My)] = OUT[i];
+    if (pol == SC_ST_PLAIN) {
+      for (int i = tid; i < Mx * My; i += 256) xhat[f3_shard_index(sh, img, i, My)] = OUT[i];
+    } else if (pol == SC_ST_WT) {
+      for (int i = tid; i < Mx * My; i += 256) sc_store8_wt(xhat + f3_shard_index(sh, img, i, My), OUT[i]);
+    } else {
+      for (int i = tid; i < Mx * My; i += 256) sc_store8_nt(xhat + f3_shard_index(sh, img, i, My), OUT[i]);
+    }
   }
 }
 
@@ -785,9 +814,11 @@ static void fft3_launch_inv(const Fft2dPlan* fp, const cf32* yhat, IO* y, const 
 // x / y: float32, or bfloat16 storage when the plan carries SC_PLAN_IO_BF16 (IO = sc_bf16)
 template <typename IO>
 static inline int fft3_forward(const Fft2dPlan* fp, int mode, const IO* x, cf32* xhat, int64_t n_images,
-                               sc_stream_t st, std::string* err, F3Shard sh = F3Shard{0, 0}) {
+                               sc_stream_t st, std::string* err, F3Shard sh = F3Shard{0, 0},
+                               int st_pol = SC_ST_PLAIN /* store policy of xhat, sc_device.h */) {
   const float s_dc = (mode == 0) ? fp->sf : fp->si;
   const float s_other = (mode == 0) ? fp->sf : 2.f * fp->si;
+  sh.st_pol = st_pol;
   switch (fp->H) {
     case 64: fft3_launch_fwd<64, IO>(fp, x, xhat, n_images, s_dc, s_other, st, sh); break;
     case 128: fft3_launch_fwd<128, IO>(fp, x, xhat, n_images, s_dc, s_other, st, sh); break;

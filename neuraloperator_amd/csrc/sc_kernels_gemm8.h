@@ -48,7 +48,10 @@ struct Gemm8Args {
   int64_t a_sp, a_sr, b_sr, b_sq, c_sp, c_sq;   // complex elements; the mode stride of all three is 1
   int64_t a_sg, b_sg, c_sg;    // element offset from one group of 16 modes to the next (16 for plain arrays; anything
                                // for a group-major "tiled spectrum": [group][row][col][16 modes])
-  int stream_c;                // 1: C is not read by the next kernel -> non-temporal stores
+  int stream_c;                // store policy of C (sc_device.h): SC_ST_PLAIN; SC_ST_NT: C is not read by the next kernel
+                               // -> non-temporal stores; SC_ST_WT: the next kernel reads it -> write-through stores
+  int nt_a, nt_b;              // 1: every piece of the operand has ONE reader in this launch (n_qb == 1 / n_pb == 1) and
+                               // the caller calls it cold -> its LDS-DMA requests are non-temporal (plain stage loop only)
 };
 
 template <int GS, int QT, int SUB = 1>
@@ -94,13 +97,24 @@ struct Gemm8Cfg {
 #endif
 
 #ifndef SC_EMU
-SC_DEVICE void sc_store16(cf32* dst, const sc_f4 v, const int stream) {
-  if (stream) __builtin_nontemporal_store(v, reinterpret_cast<sc_f4*>(dst));
+template <int POLICY>
+SC_DEVICE void sc_store16(cf32* dst, const sc_f4 v) {
+  if (POLICY == SC_ST_WT) sc_store16_wt(dst, v);
+  else if (POLICY == SC_ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<sc_f4*>(dst));
   else *reinterpret_cast<sc_f4*>(dst) = v;
 }
 #else
-inline void sc_store16(cf32* dst, const sc_f4 v, const int) { std::memcpy(dst, &v, 16); }
+template <int POLICY>
+inline void sc_store16(cf32* dst, const sc_f4 v) { std::memcpy(dst, &v, 16); }
 #endif
+// f(policy as a compile-time constant) under a wave-uniform branch on the run-time policy: a group of stores takes the
+// branch once, and each copy of the group is straight-line code of one store form
+template <typename F>
+SC_DEVICE void sc_store_policy_dispatch(const int policy, F&& f) {
+  if (policy == SC_ST_WT) f(std::integral_constant<int, SC_ST_WT>());
+  else if (policy == SC_ST_NT) f(std::integral_constant<int, SC_ST_NT>());
+  else f(std::integral_constant<int, SC_ST_PLAIN>());
+}
 
 // wait until the stage needed now has landed: in the steady state exactly NEWER stages (PPW LDS-DMA instructions
 // per wave each) were requested after it and stay in flight; near the end of the r loop fewer exist and the wave
@@ -193,26 +207,38 @@ SC_DEVICE void g8_workgroup(const Gemm8Args& g, const cf32* __restrict__ A, cons
     for (int j = 0; j < NBW; ++j) pB[j] = srcB[j] + (int64_t)rb_k[j] * g.b_sr;
     int r_next = 0;                                       // first r of the next r pair to request
     // piece pc of a stage: r pair sub = pc / (1 + NBW); its A piece first, then its NBW B pieces
-    auto issue_piece = [&](const int buf, const int pc) {
+    // POL (compile time): may this copy of the code issue non-temporal requests (g.nt_a / g.nt_b, wave-uniform)?  The copy
+    // without them is the request sequence of rounds 2-7, untouched
+    auto issue_piece = [&](const int buf, const int pc, auto POL) {
+      constexpr bool pol = decltype(POL)::value;
       sc_f4* sb = lds + buf * K::STAGE_G;
       const int sub = pc / (1 + NBW), e = pc % (1 + NBW);
       if (e == 0) {
         const int64_t backA = (r_next + ra_k < g.R) ? 0 : (int64_t)(r_next + ra_k - (g.R - 1)) * g.a_sr;
-        SC_GLDS16(pA - backA, sb + sub * K::SUB_G + w * 64);
+        if (pol && g.nt_a) SC_GLDS16_AUX(pA - backA, sb + sub * K::SUB_G + w * 64, SC_AUX_NT);
+        else SC_GLDS16(pA - backA, sb + sub * K::SUB_G + w * 64);
         pA += stepA;
       }
 #pragma unroll
       for (int j = 0; j < NBW; ++j)
         if (e == 1 + j) {
           const int64_t backB = (r_next + rb_k[j] < g.R) ? 0 : (int64_t)(r_next + rb_k[j] - (g.R - 1)) * g.b_sr;
-          SC_GLDS16(pB[j] - backB, sb + sub * K::SUB_G + K::A_G + (w + K::NW * j) * 64);
+          if (pol && g.nt_b) SC_GLDS16_AUX(pB[j] - backB, sb + sub * K::SUB_G + K::A_G + (w + K::NW * j) * 64, SC_AUX_NT);
+          else SC_GLDS16(pB[j] - backB, sb + sub * K::SUB_G + K::A_G + (w + K::NW * j) * 64);
           pB[j] += stepB;
         }
       if (e == NBW) r_next += 2;
     };
+    // ONE wave-uniform branch per stage in front of the default sequence; the software-pipelined form issues its requests
+    // piece by piece between MFMAs and keeps the one request form it was tuned with
     auto issue = [&](const int buf) {
+      if (!IL && (g.nt_a | g.nt_b)) {
 #pragma unroll
-      for (int pc = 0; pc < K::PPW; ++pc) issue_piece(buf, pc);
+        for (int pc = 0; pc < K::PPW; ++pc) issue_piece(buf, pc, std::true_type());
+      } else {
+#pragma unroll
+        for (int pc = 0; pc < K::PPW; ++pc) issue_piece(buf, pc, std::false_type());
+      }
     };
     struct Ops {                 // MFMA operands of one stage: (Re, Im) of both modes for this lane's row / columns
       sc_f4 a;
@@ -366,7 +392,7 @@ SC_DEVICE void g8_workgroup(const Gemm8Args& g, const cf32* __restrict__ A, cons
         SC_SCHED_BARRIER();
         // filler m: one piece of work for the NEXT stages, issued while the matrix pipe is busy
         if (m < K::PPW) {
-          if (refill) issue_piece(st % D, m);
+          if (refill) issue_piece(st % D, m, std::false_type());
         } else if (m < K::PPW + NF) {
           const int f = m - K::PPW, fs = f / (1 + QT), fe = f % (1 + QT);
           if (more) {
@@ -419,20 +445,22 @@ SC_DEVICE void g8_workgroup(const Gemm8Args& g, const cf32* __restrict__ A, cons
         sc_f4 val[K::EPW];
 #pragma unroll
         for (int e = 0; e < K::EPW; ++e) val[e] = lds[(w * K::EPW + e) * 64 + lane];
+        sc_store_policy_dispatch(g.stream_c, [&](auto POL) SC_ALWAYS_INLINE_LAMBDA {
 #pragma unroll
-        for (int e = 0; e < K::EPW; ++e) {
-          const int sbase = (w * K::EPW + e) * K::SP;            // first segment of this store (uniform)
-          const int prow_ = p0 + h * 16 + (sbase >> 5);          // uniform
-          const int col = (sbase & 31) + sc_opaque(ls);
-          const int qc = q0 + col;
-          const int gr = ltq ^ ((col >> K::SH) & (GS - 1));
+          for (int e = 0; e < K::EPW; ++e) {
+            const int sbase = (w * K::EPW + e) * K::SP;            // first segment of this store (uniform)
+            const int prow_ = p0 + h * 16 + (sbase >> 5);          // uniform
+            const int col = (sbase & 31) + sc_opaque(ls);
+            const int qc = q0 + col;
+            const int gr = ltq ^ ((col >> K::SH) & (GS - 1));
 #ifdef SC_G8_ABL_NOSTORE
-          asm volatile("" ::"v"(val[e]));
-          if (g.P < 0)
+            asm volatile("" ::"v"(val[e]));
+            if (g.P < 0)
 #endif
-          if (full || (prow_ < g.P && qc < g.Q))
-            sc_store16(C + (int64_t)prow_ * g.c_sp + (int64_t)qc * g.c_sq + mC + 2 * gr, val[e], g.stream_c);
-        }
+            if (full || (prow_ < g.P && qc < g.Q))
+              sc_store16<decltype(POL)::value>(C + (int64_t)prow_ * g.c_sp + (int64_t)qc * g.c_sq + mC + 2 * gr, val[e]);
+          }
+        });
       }
     } else {
       const int pslot = ((w ^ ((qq >> K::SH) & (GS - 1))) * 4 + d) + qq * 4 * GS;   // + patch row * 64 GS + 2 j
@@ -462,20 +490,22 @@ SC_DEVICE void g8_workgroup(const Gemm8Args& g, const cf32* __restrict__ A, cons
               val[e].w = -val[e].w;
             }
           }
+          sc_store_policy_dispatch(g.stream_c, [&](auto POL) SC_ALWAYS_INLINE_LAMBDA {
 #pragma unroll
-          for (int e = 0; e < K::EPW; ++e) {
-            const int sbase = (w * K::EPW + e) * K::SP;            // first segment of this store (uniform)
-            const int prow_ = p0 + h * K::RP + (sbase >> 4);       // uniform
-            const int col = (sbase & 15) + sc_opaque(ls);
-            const int qc = q0 + u * 16 + col;
-            const int gr = ltq ^ ((col >> K::SH) & (GS - 1));
+            for (int e = 0; e < K::EPW; ++e) {
+              const int sbase = (w * K::EPW + e) * K::SP;            // first segment of this store (uniform)
+              const int prow_ = p0 + h * K::RP + (sbase >> 4);       // uniform
+              const int col = (sbase & 15) + sc_opaque(ls);
+              const int qc = q0 + u * 16 + col;
+              const int gr = ltq ^ ((col >> K::SH) & (GS - 1));
 #ifdef SC_G8_ABL_NOSTORE             // measurement builds only: everything but the C stores
-            asm volatile("" ::"v"(val[e]));
-            if (g.P < 0)
+              asm volatile("" ::"v"(val[e]));
+              if (g.P < 0)
 #endif
-            if (full || (prow_ < g.P && qc < g.Q))
-              sc_store16(C + (int64_t)prow_ * g.c_sp + (int64_t)qc * g.c_sq + mC + 2 * gr, val[e], g.stream_c);
-          }
+              if (full || (prow_ < g.P && qc < g.Q))
+                sc_store16<decltype(POL)::value>(C + (int64_t)prow_ * g.c_sp + (int64_t)qc * g.c_sq + mC + 2 * gr, val[e]);
+            }
+          });
         }
       }
     }

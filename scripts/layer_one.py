@@ -3,6 +3,7 @@ times.  Every kernel of the step appears with its in-step cache state.
 
     LAYER_SHAPE = "B,C,spatial...,modes..."   (default: the metric shape 32,64,256,256,64,64)
     LAYER_IO    = f32 | bf16                  bf16: SC_PLAN_IO_BF16 real tensors (BASELINE configs[1])
+    LAYER_FLAGS = <int>                       dense: extra SC_PLAN_* bits (1024 = SC_PLAN_PLAIN_CACHE_POLICY, round 7's policy)
     LAYER_KIND  = dense | tucker              dense: sc_layer_forward / _backward through the C-ABI (tests/engine_runner);
                                               tucker: the drop-in module with Tucker rank 0.1, factorized (configs[2])
 """
@@ -42,7 +43,7 @@ if kind == "tucker":
 else:
     w = torch.randn(C, C, *kept, dtype=torch.cfloat, device=dev)
     bias = torch.randn(C, *([1] * nd), device=dev)
-    flags = _lib.SC_PLAN_IO_BF16 if io == "bf16" else 0
+    flags = (_lib.SC_PLAN_IO_BF16 if io == "bf16" else 0) | int(os.environ.get("LAYER_FLAGS", 0))
     for _ in range(reps):
         layer_fwd_bwd(lib, x, w, bias, g, kept, kept, flags=flags)
 torch.cuda.synchronize()
