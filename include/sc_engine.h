@@ -324,6 +324,34 @@ typedef struct {
 } sc_specop_desc;
 int sc_spectral_op(const sc_specop_desc* desc, const float* xhat, float* yhat, void* stream);
 
+/* ---- divergence-free (Helmholtz-Hodge) spectral projection ----
+ * The step between the two transforms of neuralop/layers/spectral_projection.py's
+ * spectral_projection_divergence_free (:6-102): the spectra of the ndim components of a vector field times the per-mode
+ * projector, which does not factor into per-axis tables.  T[d]: a REAL fp32 device table [kept[d]][2][3] in the plan's
+ * row order; entry [i][s] = (kappa, keep, z) of row i for s = 0 (the mode itself) and s = 1 (its mirror -k): the
+ * wavenumber the row is assigned, whether it is kept (0 / 1) and whether it is the row of the zeroed mode (0 / 1).
+ *   per mode m and sign s:  K_c = kappa_{sel[c]},  w = prod_d keep_d * (1 - prod_d z_d),
+ *                           G_ab = w (delta_ab - K_a K_b / (sum_c K_c^2 + eps))
+ *   yhat[g, a, m] = sum_b 1/2 (G+_ab + G-_ab) xhat[g, b, m]
+ * (the real multiplier under which irfftn(. rfftn(u)) equals real(ifftn(G fftn(u))) for real u).  xhat (groups, ndim,
+ * kept[0..ndim-1]) complex64 contiguous; yhat element (g, a, m) lies at complex offset g * y_group_stride +
+ * a * y_comp_stride + m.  yhat == xhat is allowed with the source's strides (every lane loads all of its sources
+ * before its first store); buffers that overlap in any other way are not.  Every addressed yhat element is
+ * overwritten.  8-byte alignment of xhat / yhat suffices.  Refused before any launch: ndim outside 2..3, sel outside
+ * [0, ndim), a null pointer, a non-positive extent, a negative stride, eps <= 0.  No LDS, no atomics, fixed summation
+ * order: deterministic.  At most 3 ndim + 2 roundings per real component of an output (sc_kernels_helmholtz.h). */
+typedef struct {
+  int32_t ndim;                               /* 2..3 mode dims = components                               */
+  int32_t sel[3];                             /* the axis whose kappa component c takes                    */
+  float eps;
+  int32_t reserved;
+  int64_t kept[3];
+  int64_t groups;
+  int64_t y_group_stride, y_comp_stride;      /* complex elements                                          */
+  const float* T[3];
+} sc_helmholtz_desc;
+int sc_helmholtz_project(const sc_helmholtz_desc* desc, const float* xhat, float* yhat, void* stream);
+
 /* ---- banded real-space operators: finite differences and the Lp / H1 data losses ----
  * neuralop/losses/differentiation.py's FiniteDiff (:11-660) is, along one axis, an N x N matrix with three interior
  * bands and (non-periodic) two one-sided boundary rows of four entries; it, its transpose and D^T D are banded with

@@ -20,6 +20,7 @@ from .discrete_continuous_convolution import (DiscreteContinuousConv2d, Discrete
                                               EquidistantDiscreteContinuousConvTranspose2d)
 from .local_no_block import LocalNOBlocks  # noqa: F401
 from .attention import AttentionKernelIntegral, RotaryEmbedding2D  # noqa: F401
+from .spectral_projection import HelmholtzProjection, spectral_projection_divergence_free  # noqa: F401
 from .graph import GraphedStep, capture_step  # noqa: F401
 
 __version__ = "0.1.0"

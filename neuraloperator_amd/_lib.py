@@ -129,6 +129,12 @@ class SpecopDesc(Structure):                                # sc_specop_desc
                 ("A", c_void_p * 3), ("B", c_void_p * 3)]
 
 
+class HelmholtzDesc(Structure):                             # sc_helmholtz_desc
+    _fields_ = [("ndim", c_int32), ("sel", c_int32 * 3), ("eps", ctypes.c_float), ("reserved", c_int32),
+                ("kept", c_int64 * 3), ("groups", c_int64), ("y_group_stride", c_int64), ("y_comp_stride", c_int64),
+                ("T", c_void_p * 3)]
+
+
 SC_BAND_MAX_TERMS = 12
 
 
@@ -291,6 +297,7 @@ class ScEngineLib:
                "sc_pointwise_linear_workspace_bytes_ex", "sc_pointwise_linear_backward_ex", "sc_pointwise_block_backward",
                "sc_pointwise_block_backward_supported", "sc_bicubic_rows_forward", "sc_bicubic_rows_backward",
                "sc_wire_pack_c32", "sc_wire_unpack_c32", "sc_legendre_analysis", "sc_legendre_synthesis", "sc_spectral_op",
+               "sc_helmholtz_project",
                "sc_band_apply", "sc_sobolev_workspace_bytes", "sc_sobolev_sums", "sc_lp_grad", "sc_radius_count",
                "sc_radius_fill", "sc_csr_transpose_workspace_bytes", "sc_csr_transpose", "sc_csr_reduce",
                "sc_csr_edge_grad", "sc_edge_lift", "sc_edge_lift_bwd", "sc_fdconv_path", "sc_fdconv_workspace_bytes",
@@ -454,6 +461,8 @@ class ScEngineLib:
             getattr(L, s).restype = c_int
         L.sc_spectral_op.argtypes = [POINTER(SpecopDesc), c_void_p, c_void_p, c_void_p]
         L.sc_spectral_op.restype = c_int
+        L.sc_helmholtz_project.argtypes = [POINTER(HelmholtzDesc), c_void_p, c_void_p, c_void_p]
+        L.sc_helmholtz_project.restype = c_int
         L.sc_band_apply.argtypes = [POINTER(BandDesc), c_void_p, c_void_p, c_void_p, c_void_p]
         L.sc_band_apply.restype = c_int
         L.sc_sobolev_workspace_bytes.argtypes = [POINTER(SobolevDesc)]
@@ -843,6 +852,21 @@ class ScEngineLib:
             for i in range(nd):
                 d.term_tab[j][i] = tab[i]
         self._check(self.lib.sc_spectral_op(byref(d), x_ptr, y_ptr, stream))
+
+    def helmholtz_project(self, x_ptr, y_ptr, *, kept, groups, sel, eps, tabs, y_group_stride, y_comp_stride, stream=0):
+        """yhat[g, a] = sum_b 1/2 (G+_ab + G-_ab) xhat[g, b] with the per-mode projector G of sc_helmholtz_project;
+        tabs the device pointers of the per-axis tables [kept_d][2][3] fp32, sel the axis whose wavenumber each
+        component takes; y_ptr may equal x_ptr"""
+        d = HelmholtzDesc()
+        nd = len(kept)
+        if not 2 <= nd <= 3 or len(sel) != nd or len(tabs) != nd:
+            raise EngineError(f"sc_helmholtz_project: {nd} dims with {len(sel)} sel entries and {len(tabs)} tables "
+                              "(2 or 3 dims, one of each per dim)")
+        d.ndim, d.eps, d.groups = nd, eps, groups
+        d.y_group_stride, d.y_comp_stride = y_group_stride, y_comp_stride
+        for i in range(nd):
+            d.kept[i], d.sel[i], d.T[i] = kept[i], sel[i], tabs[i]
+        self._check(self.lib.sc_helmholtz_project(byref(d), x_ptr, y_ptr, stream))
 
     def band_apply(self, u_ptr, u2_ptr, y_ptr, *, dims, periodic, groups, n_src, n_out, terms, tabs, n_tab,
                    y_group_stride, y_out_stride, scale=0, scale_mul=0, stream=0):

@@ -47,6 +47,7 @@
 #include "sc_kernels_bicubic.h"
 #include "sc_kernels_sht.h"
 #include "sc_kernels_specop.h"
+#include "sc_kernels_helmholtz.h"
 #include "sc_kernels_stencil.h"
 #include "sc_kernels_wire.h"
 #include "sc_host_common.h"
@@ -2871,6 +2872,59 @@ extern "C" int sc_spectral_op(const sc_specop_desc* d, const float* xhat, float*
   const dim3 grid((unsigned)rows, (unsigned)tiles, (unsigned)((d->groups + gpw - 1) / gpw));
   SC_LAUNCH(k_spectral_op, grid, dim3(256), 0, (sc_stream_t)stream, xhat, yhat, a);
   return sc_check_launch("k_spectral_op");
+}
+
+// ---- divergence-free spectral projection (sc_kernels_helmholtz.h) --------------------------------------------------
+extern "C" int sc_helmholtz_project(const sc_helmholtz_desc* d, const float* xhat, float* yhat, void* stream) {
+  SC_CHECK_ARG(d, "null argument");
+  SC_CHECK_ARG(d->ndim >= 2 && d->ndim <= 3, "helmholtz_project: ndim must be 2 or 3");
+  SC_CHECK_ARG(d->groups >= 0 && d->groups < ((int64_t)1 << 40), "helmholtz_project: group count out of range");
+  SC_CHECK_ARG(d->eps > 0.f && d->eps < 1e30f, "helmholtz_project: eps must be positive and finite");
+  int64_t rows = 1;
+  for (int i = 0; i < d->ndim; ++i) {
+    SC_CHECK_ARG(d->kept[i] >= 1 && d->kept[i] < (1 << 24), "helmholtz_project: mode extent out of range");
+    SC_CHECK_ARG(d->sel[i] >= 0 && d->sel[i] < d->ndim, "helmholtz_project: sel names no axis");
+    if (i < d->ndim - 1) rows *= d->kept[i];
+  }
+  const int64_t kl = d->kept[d->ndim - 1];
+  SC_CHECK_ARG(rows < ((int64_t)1 << 31) - 1 && rows * kl < ((int64_t)1 << 40), "helmholtz_project: spectrum too large");
+  SC_CHECK_ARG(d->y_group_stride >= 0 && d->y_comp_stride >= 0, "helmholtz_project: negative output stride");
+  SC_CHECK_ARG(xhat && yhat, "null argument");
+  for (int i = 0; i < d->ndim; ++i) SC_CHECK_ARG(d->T[i], "helmholtz_project: null table");
+  // in place: a lane stores where it loaded only if the result has the source's layout
+  SC_CHECK_ARG(xhat != yhat || (d->y_comp_stride == rows * kl && d->y_group_stride == d->ndim * rows * kl),
+               "helmholtz_project: an in-place call takes the source's strides");
+  if (d->groups == 0) return 0;
+  HelmArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.t_last = d->T[d->ndim - 1];
+  for (int i = 0; i < d->ndim - 1; ++i) {
+    a.t_row[i] = d->T[i];
+    a.k_row[i] = (int)d->kept[i];
+  }
+  for (int i = 0; i < d->ndim; ++i) a.sel[i] = d->sel[i];
+  a.groups = d->groups;
+  a.y_gs = d->y_group_stride;
+  a.y_cs = d->y_comp_stride;
+  a.n_row_axes = d->ndim - 1;
+  a.kl = (int)kl;
+  a.rows = (int)rows;
+  a.eps = d->eps;
+  // the split of sc_spectral_op: waves side by side along the row 1 up to 128 columns, 2 up to 256, 4 above; up to 8
+  // groups per workgroup while that leaves 2048 workgroups, more where the grid limits ask for it
+  a.col_waves_log2 = kl > 256 ? 2 : kl > 128 ? 1 : 0;
+  const int64_t tile = (int64_t)128 << a.col_waves_log2;
+  const int64_t tiles = (kl + tile - 1) / tile;
+  SC_CHECK_ARG(tiles <= 65535, "helmholtz_project: last mode extent too large");
+  int64_t gpw = 8;
+  while (gpw > 1 && rows * tiles * ((d->groups + gpw - 1) / gpw) < 2048) gpw >>= 1;
+  while ((d->groups + gpw - 1) / gpw > 65535 || rows * tiles * ((d->groups + gpw - 1) / gpw) >= ((int64_t)1 << 23))
+    gpw <<= 1;
+  a.gpw = (int)gpw;
+  const dim3 grid((unsigned)rows, (unsigned)tiles, (unsigned)((d->groups + gpw - 1) / gpw));
+  if (d->ndim == 2) SC_LAUNCH(k_helmholtz_project<2>, grid, dim3(256), 0, (sc_stream_t)stream, xhat, yhat, a);
+  else SC_LAUNCH(k_helmholtz_project<3>, grid, dim3(256), 0, (sc_stream_t)stream, xhat, yhat, a);
+  return sc_check_launch("k_helmholtz_project");
 }
 
 // ---- banded real-space operators: finite differences, Lp / H1 losses (sc_kernels_stencil.h) ------------------------

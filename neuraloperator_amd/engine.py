@@ -986,6 +986,90 @@ class SpectralOpFn(torch.autograd.Function):
         return SpectralOpFn.apply(g, ctx.tabs, back, ctx.n_src, not ctx.conj, False), None, None, None, None, None
 
 
+# ---- divergence-free spectral projection (sc_helmholtz_project) --------------------------------------------------
+class HelmholtzTables:
+    """Per-axis tables of sc_helmholtz_project on one device: t[d] fp32 (kept_d, 2, 3) in the plan's row order, entry
+    [i, s] = (kappa, keep, z) of row i for s = 0 (the mode) and s = 1 (its mirror).  ``sel[c]`` is the axis whose kappa
+    component c takes.  Built once by the caller (float64, rounded once to fp32); constants of the operator."""
+
+    def __init__(self, t, sel, eps):
+        if not 2 <= len(t) <= 3 or len(sel) != len(t) or any(not 0 <= int(s) < len(t) for s in sel):
+            raise ValueError("helmholtz tables: one table and one sel entry in [0, ndim) per mode dim, 2 or 3 dims")
+        for x in t:
+            if x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[1:]) != (2, 3) or not x.is_contiguous() \
+                    or x.device != t[0].device:
+                raise ValueError("helmholtz tables: contiguous fp32 (kept, 2, 3) tables on one device")
+        if not float(eps) > 0:
+            raise ValueError("helmholtz tables: eps must be positive")
+        self.t, self.sel, self.eps = list(t), tuple(int(s) for s in sel), float(eps)
+        self.kept = tuple(int(x.shape[0]) for x in t)
+        self.device = t[0].device
+        self.ptrs = [x.data_ptr() for x in self.t]
+
+
+_HELM_TABLES = collections.OrderedDict()       # (device, key of the caller) -> HelmholtzTables, least recently used first
+
+
+def get_helmholtz_tables(device, key, build):
+    """Cached device tables, as get_spectral_tables: ``key`` names the operator (grid, lengths, modes), ``build()``
+    returns (host tables, sel, eps) on a miss."""
+    dev = torch.device(device)
+    full = (dev.type, dev.index if dev.index is not None or dev.type != "cuda" else torch.cuda.current_device(), key)
+    with _PLAN_LOCK:
+        tabs = _HELM_TABLES.get(full)
+        if tabs is not None:
+            _HELM_TABLES.move_to_end(full)
+            return tabs
+    t, sel, eps = build()
+    tabs = HelmholtzTables([x.to(dev) for x in t], sel, eps)
+    with _PLAN_LOCK:
+        _HELM_TABLES[full] = tabs
+        while len(_HELM_TABLES) > MAX_CACHED_SPEC_TABLES:
+            _HELM_TABLES.popitem(last=False)
+    return tabs
+
+
+class HelmholtzProjectFn(torch.autograd.Function):
+    """u (groups, ndim, *spatial) fp32 -> its projection, the same shape: ONE real forward transform onto the block
+    ``tabs.kept`` (pruned where that is smaller than the half spectrum), ONE sc_helmholtz_project launch in place, ONE
+    inverse transform.  The operator is its own adjoint -- the multiplier is real, symmetric in the components and even
+    in k, and the kept block holds the mirror of every mode it holds -- so backward is forward on the cotangent."""
+
+    @staticmethod
+    def forward(ctx, u, tabs):
+        ctx.tabs = tabs
+        _require_gpu(u, "field")
+        _require_gpu(tabs.t[0], "helmholtz tables")
+        if tabs.device != u.device:
+            raise ValueError(f"helmholtz tables on {tabs.device}, field on {u.device}")
+        u = u.contiguous().float()
+        spatial, kept = [int(s) for s in u.shape[2:]], tabs.kept
+        groups, nc = int(u.shape[0]), int(u.shape[1])
+        if nc != len(kept) or len(spatial) != len(kept):
+            raise ValueError(f"field {tuple(u.shape)} against helmholtz tables for {len(kept)} components")
+        # the three C-ABI calls on one plan (unscaled forward, 1/N on the way back) and one workspace: at small grids
+        # the step is bound by the host's issue rate, so nothing is looked up or allocated twice
+        lib = _lib.get_lib()
+        plan = get_plan(u.device, spatial, kept, "backward", 0)
+        modes, n = math.prod(kept), groups * nc
+        with torch.cuda.device(u.device):
+            ws = _ws(lib.plan_workspace_bytes(plan, n), u.device)
+            xhat = torch.empty((groups, nc, *kept, 2), dtype=torch.float32, device=u.device)
+            y = torch.empty_like(u)
+            stream = _stream()
+            lib.transform_forward(plan, _lib.SC_FWD_SCALED, u.data_ptr(), xhat.data_ptr(), n, ws.data_ptr(), stream)
+            lib.helmholtz_project(xhat.data_ptr(), xhat.data_ptr(), kept=kept, groups=groups, sel=tabs.sel,
+                                  eps=tabs.eps, tabs=tabs.ptrs, y_group_stride=nc * modes, y_comp_stride=modes,
+                                  stream=stream)
+            lib.transform_inverse(plan, _lib.SC_INV_PADDED, xhat.data_ptr(), 0, nc, y.data_ptr(), n, ws.data_ptr(),
+                                  stream)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return HelmholtzProjectFn.apply(g.contiguous(), ctx.tabs), None
+
+
 # ---- banded real-space operators: finite differences and the Lp / H1 losses (sc_band_apply, sc_sobolev_sums) -------
 BAND_HALF = 3                                  # half-width of every table: taps -3 .. 3
 
