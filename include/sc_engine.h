@@ -751,11 +751,16 @@ int sc_bias_grad(const sc_plan* plan, const float* ghat, int64_t batch, int64_t 
  * (_contract_tucker, neuralop/layers/spectral_convolution.py:76-103: the two mode factors absorbed into the core; fg =
  * the (in-rank, out-rank) pairs).  All arrays complex64 interleaved, contiguous: core (fg, rx, ry), ux (mx, rx),
  * uy (my, ry), t (fg, mx, my).  Backward: gcore / gux / guy overwritten, workspace sc_tucker_modes_workspace_bytes(d).
- * Limits: mx, my, rx, ry <= 64, my ry <= 1024 (sc_tucker_modes_supported; callers fall back to sc_modegemm). */
+ * Limits: mx, my, rx, ry <= 64, my ry <= 1024 (sc_tucker_modes_supported; callers fall back to sc_modegemm).
+ * sc_tucker_modes_path: which kernels the two calls launch (the launches switch on the same decision): 0 = unsupported,
+ * 1 = the vector kernels k_tucker_modes_fwd / _bwd (the padded layout of the matrix-core kernels passes 150 KB of LDS),
+ * else 10 f + b: f = 1..4 for k_tucker_modes_fwd_mx<4, 3>, <4, 4>, <16, 3>, <16, 4>, b = 1 for
+ * k_tucker_modes_bwd_mx<3, 9, 3, 3, 2>, 2 for <16, 16, 4, 4, 4>. */
 typedef struct sc_tucker_desc {
   int64_t fg, rx, ry, mx, my;
 } sc_tucker_desc;
 int sc_tucker_modes_supported(const sc_tucker_desc* d);
+int sc_tucker_modes_path(const sc_tucker_desc* d);
 int sc_tucker_modes_forward(const sc_tucker_desc* d, const float* core, const float* ux, const float* uy, float* t,
                             void* stream);
 size_t sc_tucker_modes_workspace_bytes(const sc_tucker_desc* d);

@@ -286,7 +286,7 @@ class ScEngineLib:
                "sc_layer_forward_ex", "sc_round_f16", "sc_pointwise_mlp_forward", "sc_pointwise_block_forward",
                "sc_pointwise_mlp_backward", "sc_pointwise_mlp_workspace_bytes", "sc_pointwise_linear_forward",
                "sc_pointwise_linear_backward", "sc_pointwise_linear_workspace_bytes", "sc_layer_backward_ex",
-               "sc_pointwise_mlp_backward_ex", "sc_tucker_modes_supported", "sc_tucker_modes_forward",
+               "sc_pointwise_mlp_backward_ex", "sc_tucker_modes_supported", "sc_tucker_modes_path", "sc_tucker_modes_forward",
                "sc_tucker_modes_backward", "sc_tucker_modes_workspace_bytes", "sc_modegemm_pair",
                "sc_modegemm_pair_fused", "sc_modegemm_pair_path", "sc_plan_workspace_bytes_sharded", "sc_transform_forward_sharded",
                "sc_transform_inverse_sharded", "sc_bias_grad_sharded", "sc_tucker_chain_forward",
@@ -417,6 +417,8 @@ class ScEngineLib:
         L.sc_pointwise_linear_backward.restype = c_int
         L.sc_tucker_modes_supported.argtypes = [POINTER(TuckerDesc)]
         L.sc_tucker_modes_supported.restype = c_int
+        L.sc_tucker_modes_path.argtypes = [POINTER(TuckerDesc)]
+        L.sc_tucker_modes_path.restype = c_int
         L.sc_tucker_modes_forward.argtypes = [POINTER(TuckerDesc)] + [c_void_p] * 5
         L.sc_tucker_modes_forward.restype = c_int
         L.sc_tucker_modes_workspace_bytes.argtypes = [POINTER(TuckerDesc)]
@@ -722,6 +724,11 @@ class ScEngineLib:
 
     def tucker_modes_supported(self, fg, rx, ry, mx, my):
         return bool(self.lib.sc_tucker_modes_supported(byref(TuckerDesc(fg, rx, ry, mx, my))))
+
+    def tucker_modes_path(self, fg, rx, ry, mx, my):
+        """0: unsupported, 1: the vector kernels, else 10 f + b: forward k_tucker_modes_fwd_mx<4, 3>, <4, 4>, <16, 3>,
+        <16, 4> for f = 1..4, backward k_tucker_modes_bwd_mx<3, 9, 3, 3, 2> for b = 1, <16, 16, 4, 4, 4> for b = 2."""
+        return int(self.lib.sc_tucker_modes_path(byref(TuckerDesc(fg, rx, ry, mx, my))))
 
     def tucker_modes_forward(self, fg, rx, ry, mx, my, core, ux, uy, t, stream=0):
         self._check(self.lib.sc_tucker_modes_forward(byref(TuckerDesc(fg, rx, ry, mx, my)), core, ux, uy, t, stream))

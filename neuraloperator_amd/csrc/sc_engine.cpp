@@ -2561,6 +2561,29 @@ extern "C" int sc_tucker_modes_supported(const sc_tucker_desc* d) {
   return tucker_lds_bytes(d, true) <= 150 * 1024 ? 1 : 0;
 }
 
+// The kernels of a supported problem, decided in ONE place: the two launch functions switch on it and
+// sc_tucker_modes_path reports it.  mx = matrix cores; fwd 1..4 = k_tucker_modes_fwd_mx<4, 3>, <4, 4>, <16, 3>, <16, 4>
+// (prefetch registers for Rx Ry <= 1024 or more, three or four 16-blocks of y); bwd 1 = k_tucker_modes_bwd_mx<3, 9, 3, 3, 2>,
+// the smallest instantiation that holds ranks (36, ., 36, 19) on 64 x 33 kept modes, 2 = <16, 16, 4, 4, 4>
+struct TuckerRoute {
+  bool mx;
+  int fwd, bwd;
+};
+static TuckerRoute tucker_route(const sc_tucker_desc* d) {
+  TuckerRoute r;
+  r.mx = tucker_use_mx(d);
+  const bool few = d->rx * d->ry <= 4 * 256, y3 = d->my <= 48;
+  r.fwd = few ? (y3 ? 1 : 2) : (y3 ? 3 : 4);
+  r.bwd = (d->rx * d->ry <= 3 * 256 && d->mx * d->my <= 9 * 256 && d->rx <= 48 && d->my <= 48 && d->ry <= 32) ? 1 : 2;
+  return r;
+}
+
+extern "C" int sc_tucker_modes_path(const sc_tucker_desc* d) {
+  if (!sc_tucker_modes_supported(d)) return 0;
+  const TuckerRoute r = tucker_route(d);
+  return r.mx ? 10 * r.fwd + r.bwd : 1;
+}
+
 template <typename K>
 static int tucker_launch(K kernel, const TuckerModesArgs& g, size_t lds, sc_stream_t st, const char* what) {
 #ifndef SC_EMU
@@ -2579,14 +2602,16 @@ extern "C" int sc_tucker_modes_forward(const sc_tucker_desc* d, const float* cor
   g.core = (const cf32*)core; g.ux = (const cf32*)ux; g.uy = (const cf32*)uy; g.gt = nullptr; g.t = (cf32*)t; g.partial = nullptr;
   g.FG = (int)d->fg; g.Rx = (int)d->rx; g.Ry = (int)d->ry; g.Mx = (int)d->mx; g.My = (int)d->my; g.n_wg = tucker_wgs(d); g.abl = tucker_abl();
   tucker_invs(g);
-  if (tucker_use_mx(d)) {
+  const TuckerRoute route = tucker_route(d);
+  if (route.mx) {
     const size_t lds = tucker_lds_bytes(d, false);
     sc_stream_t st = (sc_stream_t)stream;
-    const bool few = d->rx * d->ry <= 4 * 256, y3 = d->my <= 48;
-    if (few && y3) return tucker_launch(k_tucker_modes_fwd_mx<4, 3>, g, lds, st, "k_tucker_modes_fwd_mx");
-    if (few) return tucker_launch(k_tucker_modes_fwd_mx<4, 4>, g, lds, st, "k_tucker_modes_fwd_mx");
-    if (y3) return tucker_launch(k_tucker_modes_fwd_mx<16, 3>, g, lds, st, "k_tucker_modes_fwd_mx");
-    return tucker_launch(k_tucker_modes_fwd_mx<16, 4>, g, lds, st, "k_tucker_modes_fwd_mx");
+    switch (route.fwd) {
+      case 1: return tucker_launch(k_tucker_modes_fwd_mx<4, 3>, g, lds, st, "k_tucker_modes_fwd_mx");
+      case 2: return tucker_launch(k_tucker_modes_fwd_mx<4, 4>, g, lds, st, "k_tucker_modes_fwd_mx");
+      case 3: return tucker_launch(k_tucker_modes_fwd_mx<16, 3>, g, lds, st, "k_tucker_modes_fwd_mx");
+      default: return tucker_launch(k_tucker_modes_fwd_mx<16, 4>, g, lds, st, "k_tucker_modes_fwd_mx");
+    }
   }
   return tucker_launch(k_tucker_modes_fwd, g, tucker_lds_bytes(d, false), (sc_stream_t)stream, "k_tucker_modes_fwd");
 }
@@ -2609,10 +2634,10 @@ extern "C" int sc_tucker_modes_backward(const sc_tucker_desc* d, const float* co
   tucker_invs(g);
   sc_stream_t st = (sc_stream_t)stream;
   int rc;
-  if (tucker_use_mx(d)) {
-    // the smallest instantiation that holds the problem: (3, 9, 3, 3, 2) is ranks (36, ., 36, 19) on 64 x 33 kept modes
+  const TuckerRoute route = tucker_route(d);
+  if (route.mx) {
     const size_t lds = tucker_lds_bytes(d, true);
-    if (d->rx * d->ry <= 3 * 256 && d->mx * d->my <= 9 * 256 && d->rx <= 48 && d->my <= 48 && d->ry <= 32)
+    if (route.bwd == 1)
       rc = tucker_launch(k_tucker_modes_bwd_mx<3, 9, 3, 3, 2>, g, lds, st, "k_tucker_modes_bwd_mx");
     else
       rc = tucker_launch(k_tucker_modes_bwd_mx<16, 16, 4, 4, 4>, g, lds, st, "k_tucker_modes_bwd_mx");
@@ -2620,7 +2645,7 @@ extern "C" int sc_tucker_modes_backward(const sc_tucker_desc* d, const float* co
     rc = tucker_launch(k_tucker_modes_bwd, g, tucker_lds_bytes(d, true), st, "k_tucker_modes_bwd");
   if (rc) return rc;
   const int np = 2 * (g.Mx * g.Rx + g.My * g.Ry);
-  if (tucker_use_mx(d)) {
+  if (route.mx) {
     SC_LAUNCH(k_tucker_reduce, dim3((unsigned)((np / 2 + 15) / 16)), dim3(256), 0, st, (const cf32*)g.partial, g.n_wg, np / 2,
               g.Mx * g.Rx, (cf32*)gux, (cf32*)guy);
     return sc_check_launch("k_tucker_reduce");

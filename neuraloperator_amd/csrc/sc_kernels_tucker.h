@@ -412,7 +412,9 @@ SC_TK_HD TkmLayout tkm_layout(const int Rx, const int Ry, const int Mx, const in
   return L;
 }
 
-SC_DEVICE int tkm_div(const int i, const uint32_t inv) { return (int)(((uint64_t)(uint32_t)i * inv) >> 32); }
+// i / n with inv = ceil(2^32 / n) as 32 bits.  n = 1 (a rank-1 factor, one kept mode) gives 2^32, which arrives as 0:
+// without the select every element landed in row 0 of its padded table
+SC_DEVICE int tkm_div(const int i, const uint32_t inv) { return inv ? (int)(((uint64_t)(uint32_t)i * inv) >> 32) : i; }
 // a [rows][cols] table (<= 4096 entries) into its padded LDS rows in two phases, so that all global loads of the
 // kernel's start are in flight together: fetch into registers, store after the zero fill
 SC_DEVICE void tkm_table_fetch(const cf32* __restrict__ src, const int n, const int tid, cf32 (&v)[16]) {

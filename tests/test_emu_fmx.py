@@ -2,11 +2,14 @@
 (sc_kernels_fmx.h: k_modegemm_bfac_mx, k_modegemm_msum_mx + k_fmx_reduce) in host emulation against numpy complex128:
 the factor steps of the Tucker / CP chains and the gradients of the factors (spectral_convolution.py:55-103 and its
 autograd), GaLore's mode products.  Ragged ranks (36, 19), mode counts that do not fill the 64-mode chunks, every
-conjugation, both storage orders of the factor, several chunks per workgroup, the dispatch rule."""
+conjugation, both storage orders of the factor, several chunks per workgroup, the dispatch rule.  Then the rows of
+factor_reference.BFAC_CASES / MSUM_CASES / SLOT_CASES the emulator can afford (at least one per instantiation): route
+asserted, guarded C and workspace, rel-L2 and the element bound gamma_N S."""
 import numpy as np
 import pytest
 import torch
 
+import factor_reference as fr
 from engine_runner import emu_lib, rel_l2
 from neuraloperator_amd import _lib
 
@@ -134,3 +137,43 @@ def test_mode_summed_contraction_slot_form(lib, dims, conj):
     a128, b128 = a.numpy().astype(np.complex128), b.numpy().astype(np.complex128)
     ref = np.einsum("prm,rqm->pq", np.conj(a128) if ca else a128, np.conj(b128) if cb else b128)
     assert rel_l2(c.numpy(), ref) < 1e-5
+
+
+@pytest.mark.parametrize("name", fr.emu_rows(fr.BFAC_CASES))
+def test_factor_operand_table_on_guarded_buffers(lib, name):
+    fr.run_bfac(lib, name, torch.device("cpu"))
+
+
+@pytest.mark.parametrize("name", fr.emu_rows(fr.MSUM_CASES))
+def test_mode_summed_table_on_the_matrix_core_kernel(lib, name):
+    fr.run_msum(lib, "msum", name, torch.device("cpu"))
+
+
+@pytest.mark.parametrize("name", fr.emu_rows(fr.SLOT_CASES))
+def test_mode_summed_table_slot_form(lib, name):
+    fr.run_msum(lib, "slot", name, torch.device("cpu"))
+
+
+def test_every_instantiation_has_a_row_the_emulator_runs():
+    full, emu = fr.coverage(), fr.coverage(emu_only=True)
+    for kind, want in (("bfac", fr.BFAC_INSTANCES), ("msum", fr.MSUM_INSTANCES), ("slot", fr.SLOT_TILES)):
+        assert {i for k, i in full if k == kind} == set(want) and all(emu[(kind, i)] for i in want)
+
+
+def test_the_chunk_distribution_the_device_rows_rely_on():
+    """fmx_wgs mirrored: 1056 chunks on 256 units become 512 workgroups, 32 of which walk three chunks; one unit (the
+    emulator) changes the distribution, not the sums"""
+    c = fr.BFAC_CASES[fr.BFAC_UNEVEN]
+    n = fr.bfac_wgs(c["P"], c["R"], c["Q"], c["M"], 256)
+    assert n == 512 and c["P"] - 2 * n == 32
+    assert fr.bfac_wgs(c["P"], c["R"], c["Q"], c["M"], 1) == 4
+
+
+@pytest.mark.parametrize("kind,name", [(k, n) for k, t in (("bfac", fr.BFAC_CASES), ("msum", fr.MSUM_CASES), ("slot", fr.SLOT_CASES))
+                                       for n in sorted(t) if t[n]["gpu_only"]])
+def test_the_reference_of_a_device_only_row_sits_inside_its_own_bound(kind, name):
+    """the rows the emulator skips: gamma_N S at the smallest N the device can meet is not below what fp32 can hold"""
+    ref, S = fr.fmx_reference(kind, name)
+    r32 = ref.astype(np.complex64).astype(np.complex128)
+    n = fr.bfac_counts(fr.BFAC_CASES[name]) if kind == "bfac" else fr.n_dot(16)
+    assert (np.maximum(np.abs((r32 - ref).real), np.abs((r32 - ref).imag)) <= fr.gamma(n) * S).all()
